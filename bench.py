@@ -23,6 +23,10 @@ over ranks is reported. Rank 0 prints one JSON line.
 At N = 1 the forward is captured once as a HIP graph and replayed in the timed loop, as each rank's work is at
 N > 1 (MiddleRunner), so the 1 -> N curve compares like with like (--no-graphs: eager everywhere).
 
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given (see
+dump_outputs) and prints the line with "roofline" and "cpu_baseline" null. Everything else runs only with --full.
+
+With --full:
 Extra fields: "roofline" for the dominant kernel, chosen by measured time per step, with "roofline.kernels" holding
 one entry per hot-path kernel (the propagation -- pg_spmm3_ngram_mid_f32 at B(20,4) --, the dense layer
 pg_directgcn_dense_f32 and the head): compulsory bytes per launch / its average launch duration from HIP events
@@ -44,6 +48,17 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md chip table)
 # --partition auto by rank count (absent: middle). Per-rank 4-gram times measured on one MI355X
 AUTO_PARTITION = {2: "replicate", 3: "replicate", 4: "halo"}
+# --dump-outputs: the step's outputs in the order the model returns them, and the size of all files together
+DUMP_NAMES = ["log_probs", "embeddings"]
+DUMP_BUDGET_BYTES = 60_000_000
+DUMP_SEED = 20240
+
+
+def positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return v
 
 
 def parse():
@@ -51,7 +66,7 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     # defaults: 50 warmup steps let the GPU clocks ramp (5 warmups measured 0.915 ms/step, 50 or 200:
     # 0.846 ms at B(20,4)); the whole default run is still well under a second of GPU work
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=positive_int, default=100)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--clock-warmup-s", type=float, default=1.0,
                     help="untimed seconds of steps before the warm-up steps (clock ramp)")
@@ -69,11 +84,18 @@ def parse():
                     help="coo (default): the model reads the reference trainer's COO wiring (Data.edge_index_* = "
                     "mathcal_A_*.indices(), edge_weight_* = .values(), protgram_directgcn_trainer.py:362-367) through "
                     "csr_from_coo; graph: a prebuilt Data.graph (build_propagation_csr)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline figure "
+                    "does not need: the per-kernel roofline (eager steps timed with HIP events), its measured traffic "
+                    "(rocprofv3 counter passes, see --no-pmc), the CPU baseline (see --no-cpu-baseline) and --extra. "
+                    "Without it the line's 'roofline' and 'cpu_baseline' are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last "
+                    "timed step returned as DIR/<name>.npy (float32; a fixed seeded sample of the rows when all of "
+                    "them would exceed DUMP_BUDGET_BYTES; N>1: one set per rank, <name>_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-sample-layers", type=int, default=1)
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 FETCH_SIZE/WRITE_SIZE passes that "
                     "measure roofline.traffic (N=1 only)")
-    ap.add_argument("--extra", action="store_true", help="also time kernel variants / training step (stderr)")
+    ap.add_argument("--extra", action="store_true", help="--full: also time kernel variants / training step (stderr)")
     ap.add_argument("--chunks", type=int, default=0, help="N>1: layer-boundary exchange in this many pieces, "
                     "overlapped with the compute (1 = one exchange after the layer; 0 = by the rank's share)")
     ap.add_argument("--partition", choices=("auto", "middle", "replicate", "halo", "exchange"), default="auto",
@@ -269,6 +291,55 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
+    if world > 1:  # the slowest rank's time is the job's
+        t_max = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
+        elapsed = float(t_max[0])
+    ms_per_step = elapsed / args.steps * 1e3
+    edges_per_step = 3 * g.nnz * L
+    value = edges_per_step * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
+
+    def emit(roofline, cpu, extra):
+        if rank == 0:
+            line = {
+                "metric": "edges/sec propagated, DirectGCN fwd on 4-gram graph, 1/2/4/8 MI355X",
+                "value": round(value, 1), "unit": "edges/s", "n_gpus": world, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(ms_per_step, 6), "higher_is_better": True,
+                "scaling": "strong", "vs_baseline": None, "dtype": "bf16" if args.bf16 else "f32",
+                "data": "synthetic",
+                "config": {"workload": wl["workload"], "graph": wl["desc"],
+                           "num_nodes": N, "transitions": int(wl["E"]), "nnz_per_adjacency": g.nnz, "feat_dim": Fd,
+                           "layers": L, "layer_dims": dims, "classes": C,
+                           "propagation": "fused-norm" if args.fused_norm else "precomputed-weights",
+                           "entry": ("trainer COO (edge_index_*/edge_weight_* -> csr_from_coo)" if entry == "coo"
+                                     else "prebuilt Data.graph (build_propagation_csr)"),
+                           "parallelism": ("single" if world == 1
+                                           else f"replicate_then_middle_x{world}"
+                                           if mp is not None and mid_run.replicate
+                                           else f"middle_ghost_a2a_x{world}" if mp is not None
+                                           else f"halo_recompute_x{world}" if hp is not None
+                                           else f"node_range_x{world}"),
+                           "ghost_rows_rank0": (int(mp.recv_ids.numel()) if mp is not None and not mid_run.replicate
+                                                else None),
+                           "exchange_chunks": (mp.chunks if mp is not None and not mid_run.replicate
+                                               else (args.chunks or 4) if part is not None else None),
+                           "halo_rows_rank0": hp.layer_rows if hp is not None else None},
+                "nodes_per_sec": round(N * L * args.steps / elapsed, 1),
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+            }
+            if extra:
+                line["extra"] = extra
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+
+    if not args.full:  # a plain run: the headline figure only
+        return emit(None, None, {})
+
+    # --full from here on.
     # per-kernel launch durations: HIP events recorded on each launch's stream around every propagation, dense and
     # head launch of eager runs of the same step right after the timed region (graph replays carry no per-launch
     # events; the kernels are the same). rocprofv3's kernel trace of the same command agrees (profiles/).
@@ -295,9 +366,6 @@ def main():
     eager_ms = float(t_local[1])
     avg_ms = dict(zip(kms, (float(v) for v in t_local[2:].tolist())))
     spmm_avg_ms = avg_ms["propagation"]
-    ms_per_step = elapsed / args.steps * 1e3
-    edges_per_step = 3 * g.nnz * L
-    value = edges_per_step * args.steps / elapsed
 
     # roofline of each hot-path kernel, priced on SURVEY 8(d)'s COMPULSORY bytes per launch (its inputs once, its
     # outputs once): the floor of HBM traffic for one launch
@@ -432,36 +500,38 @@ def main():
     if args.extra and world == 1:
         extra = extra_measurements(pkg, ops, g, model, x, data, log)
 
-    if rank == 0:
-        line = {
-            "metric": "edges/sec propagated, DirectGCN fwd on 4-gram graph, 1/2/4/8 MI355X",
-            "value": round(value, 1), "unit": "edges/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 6), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "bf16" if args.bf16 else "f32", "data": "synthetic",
-            "config": {"workload": wl["workload"], "graph": wl["desc"],
-                       "num_nodes": N, "transitions": int(wl["E"]), "nnz_per_adjacency": g.nnz, "feat_dim": Fd,
-                       "layers": L, "layer_dims": dims, "classes": C,
-                       "propagation": "fused-norm" if args.fused_norm else "precomputed-weights",
-                       "entry": ("trainer COO (edge_index_*/edge_weight_* -> csr_from_coo)" if entry == "coo"
-                                 else "prebuilt Data.graph (build_propagation_csr)"),
-                       "parallelism": ("single" if world == 1
-                                       else f"replicate_then_middle_x{world}" if mp is not None and mid_run.replicate
-                                       else f"middle_ghost_a2a_x{world}" if mp is not None
-                                       else f"halo_recompute_x{world}" if hp is not None else f"node_range_x{world}"),
-                       "ghost_rows_rank0": (int(mp.recv_ids.numel()) if mp is not None and not mid_run.replicate
-                                            else None),
-                       "exchange_chunks": (mp.chunks if mp is not None and not mid_run.replicate
-                                           else (args.chunks or 4) if part is not None else None),
-                       "halo_rows_rank0": hp.layer_rows if hp is not None else None},
-            "nodes_per_sec": round(N * L * args.steps / elapsed, 1),
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-        }
-        if extra:
-            line["extra"] = extra
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    emit(roofline, cpu, extra)
+
+
+def dump_outputs(path, out, rank, world):
+    """--dump-outputs: what the last timed step returned (log-probs and L2-normalised embeddings: of all N rows at
+    N = 1, of the rank's own rows at N > 1) as float32 ``<name>.npy`` files (``<name>_rank<r>.npy`` at N > 1), at
+    most DUMP_BUDGET_BYTES over all files and ranks. Outputs too large for that are sampled: the same seeded,
+    sorted choice of rows from every output, listed in ``sample_rows.npy`` (float64: exact for any row index)."""
+    import numpy as np
+    import torch
+    outs = [o for o in (out if isinstance(out, (tuple, list)) else (out,)) if torch.is_tensor(o)]
+    names = DUMP_NAMES if len(outs) == len(DUMP_NAMES) else [f"out{i}" for i in range(len(outs))]
+    sfx = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(path, exist_ok=True)
+    if not outs:
+        return
+    rows = outs[0].size(0)
+    row_bytes = sum(4 * (o.numel() // max(1, rows)) for o in outs)
+    budget = DUMP_BUDGET_BYTES // world
+    idx = None
+    if all(o.dim() >= 1 and o.size(0) == rows for o in outs) and rows * row_bytes > budget:
+        keep = budget // (row_bytes + 8)
+        idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(rows, size=keep, replace=False))
+        np.save(os.path.join(path, f"sample_rows{sfx}.npy"), idx.astype(np.float64))
+        idx = torch.from_numpy(idx).to(outs[0].device)
+    elif sum(4 * o.numel() for o in outs) > budget:
+        raise SystemExit("--dump-outputs: outputs over the size budget and not row-aligned, nothing to sample by")
+    for name, o in zip(names, outs):
+        o = o.detach()
+        if idx is not None:
+            o = o.index_select(0, idx)
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), o.float().cpu().numpy())
 
 
 def build_workload(pkg, args, dev, keep_raw=False):

@@ -14,7 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(300)
 def test_bench_json_line_is_self_consistent():
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "5", "--warmup", "2", "--full",
                         "--no-cpu-baseline", "--no-pmc"], cwd=REPO, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -56,6 +56,32 @@ def test_bench_json_line_is_self_consistent():
     assert out["ms_per_step"] * 0.9 <= ek <= out["ms_per_step"] * 1.6 + 0.05, (out["ms_per_step"], ek)
     assert ks["propagation"]["algorithmic_bytes_per_launch"] == 411_520_000  # SURVEY 8(d) / DESIGN §4 at B(20,4)
     assert abs(ks["dense"]["algorithmic_bytes_per_launch"] - 494.7e6) < 0.5e6
+
+
+@pytest.mark.timeout(120)
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain run (no --full) measures the headline figure only ('roofline' and 'cpu_baseline' null) and
+    --dump-outputs writes the last timed step's log-probs and embeddings as float32 .npy files. On B(20,3) (8,000
+    nodes: every row fits the size budget, so no sample file)."""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--ngram", "3", "--clock-warmup-s", "0", "--dump-outputs", str(d)], cwd=REPO,
+                       capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dtype"] == "f32" and out["unit"] == "edges/s"
+    assert out["roofline"] is None and out["cpu_baseline"] is None and "extra" not in out
+    edges = 3 * out["config"]["nnz_per_adjacency"] * out["config"]["layers"]
+    assert abs(out["value"] - edges / (out["ms_per_step"] * 1e-3)) <= 2e-3 * out["value"]
+    assert sorted(p.name for p in d.iterdir()) == ["embeddings.npy", "log_probs.npy"]
+    lp, emb = np.load(d / "log_probs.npy"), np.load(d / "embeddings.npy")
+    assert lp.dtype == np.float32 and lp.shape == (8000, 20) and emb.dtype == np.float32 and emb.shape == (8000, 128)
+    # what the model's head returns: log_softmax rows (probabilities sum to 1) and L2-normalised embedding rows
+    assert np.abs(np.exp(lp.astype(np.float64)).sum(1) - 1.0).max() < 1e-5
+    assert np.abs(np.linalg.norm(emb.astype(np.float64), axis=1) - 1.0).max() < 1e-5
 
 
 @pytest.mark.timeout(300)

@@ -5,7 +5,7 @@ Correction per MI355X_MICROARCH.md §HBM: FETCH_SIZE (KiB) reports half the byte
 (16 B/lane) reads on gfx950 -> read bytes = 2 * FETCH_SIZE * 1024; WRITE_SIZE (KiB) is exact for
 16 B/lane stores -> write bytes = WRITE_SIZE * 1024. Averages over all dispatches of each kernel.
 The "dominant" kernel is the propagation kernel with the largest total duration in the FETCH_SIZE pass's trace.
-Used by bench.py (live, every N=1 run) and from the command line:
+Used by bench.py --full (live, every N=1 run) and from the command line:
 usage: tools/pmc_traffic.py <fetch_dir> <write_dir> <out.json> <workload-tag>
 """
 import collections
