@@ -192,6 +192,29 @@ class DirectGCNLayer(nn.Module):
 _P1_CACHE: dict = {}
 
 
+class Bf16InputCache:
+    """bf16 copy of a step-invariant fp32 input: converted once (the per-step conversion was a 35 us pass of config
+    5's training step) and again only when x changes -- another tensor, or a new version counter -- in place where the
+    shape and device allow, so a captured step reads the refreshed values at the same address; an input of another
+    shape or device replaces `buffer` (train.CapturedStep pins it and captures again when it was replaced). Inputs
+    must be changed with tensor in-place ops such as copy_: writes through .data, DLPack or numpy aliases do not bump
+    the version counter and are not seen."""
+
+    def __init__(self):
+        self._ref, self._version, self.buffer = None, None, None
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        xb = self.buffer
+        if xb is not None and self._ref() is x and self._version == x._version:
+            return xb
+        if xb is not None and xb.shape == x.shape and xb.device == x.device:
+            xb.copy_(x)
+        else:
+            xb = x.to(torch.bfloat16)
+        self._ref, self._version, self.buffer = weakref.ref(x), x._version, xb
+        return xb
+
+
 class ProtGramDirectGCN(nn.Module):
     """The model wrapper (protgram_directgcn.py:143-222)."""
 
@@ -225,6 +248,7 @@ class ProtGramDirectGCN(nn.Module):
         # torch.float32 (default, the reference's CPU precision) or torch.bfloat16 (bf16 storage of features,
         # aggregates and activations with fp32 accumulation; BASELINE config 5). Not part of the state_dict.
         self.compute_dtype = torch.float32
+        self._xb = Bf16InputCache()
 
     def _apply_pe(self, x: torch.Tensor) -> torch.Tensor:
         """:182-193, out of place (the reference's in-place add fails under autograd when x has no grad)."""
@@ -294,24 +318,9 @@ class ProtGramDirectGCN(nn.Module):
                 h = F.dropout(h, p=self.dropout, training=self.training)
         return h
 
-    _xb = None
-
     def bf16_input(self, x: torch.Tensor) -> torch.Tensor:
-        """bf16 copy of a step-invariant input (no PE, no gradient) in bf16 mode: converted once and again only when x
-        changes (another tensor, or a new version counter: copy_ and in-place writes bump it), in place, so a captured
-        step reads the refreshed values at the same address (train.GraphedTrainStep calls this before each replay).
-        The per-step conversion was a 35 us pass of config 5's training step."""
-        c = self._xb
-        if c is not None and c[0]() is x and c[1] == x._version:
-            return c[2]
-        if c is not None and c[2].shape == x.shape and c[2].device == x.device:
-            xb = c[2]
-            xb.copy_(x)
-        else:
-            xb = x.to(torch.bfloat16)
-        import weakref
-        self._xb = (weakref.ref(x), x._version, xb)
-        return xb
+        """The bf16 mode's cached copy of a step-invariant input (no PE, no gradient): see Bf16InputCache."""
+        return self._xb(x)
 
     def head_train_args(self):
         """(W1, b1, W2, b2, dropout p) of the decoder when ops.head_train takes it (Linear, ReLU, Dropout, Linear),

@@ -8,6 +8,7 @@ there is no CPU implementation of the product path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import functools
 import weakref
@@ -81,9 +82,22 @@ def _require_gpu(*ts):
 # constant.grad (written by the backward, read by Adam: 6 B per element per step, 0.74 GB at config 5), the layer
 # backward leaves the constant's .grad None and files the bf16 dpre here, keyed by the parameter's address, and
 # train.Adam reads it directly (pg_adam_desc_t.gtype = 1; exactly widened: the same update bits). train_step
-# switches this on around its backward and optimizer step only, and empties the table after.
+# switches this on around its backward and optimizer step only, and empties the table after (deferring_const_grads).
 _DEFER_CONST_GRAD = False
 _DEFERRED_GRADS: dict = {}
+
+
+@contextlib.contextmanager
+def deferring_const_grads(enabled: bool):
+    """One training step's scope of the deferral: on (or off) inside, the previous setting back and the table of
+    filed gradients empty after, also when the step raises."""
+    global _DEFER_CONST_GRAD
+    prev, _DEFER_CONST_GRAD = _DEFER_CONST_GRAD, bool(enabled)
+    try:
+        yield
+    finally:
+        _DEFER_CONST_GRAD = prev
+        _DEFERRED_GRADS.clear()
 
 
 def deferred_grad(p: torch.Tensor) -> Optional[torch.Tensor]:
@@ -92,8 +106,11 @@ def deferred_grad(p: torch.Tensor) -> Optional[torch.Tensor]:
 
 
 def _defer_const(constant, need: bool, M: int, rows) -> bool:
+    """Only a leaf that requires grad is what train.Adam steps and looks up by address: any other constant (a derived
+    tensor) takes the normal .grad path."""
     return (_DEFER_CONST_GRAD and need and constant is not None and constant.dtype == torch.float32 and rows is None
-            and constant.dim() == 2 and constant.size(0) == M and constant.is_contiguous())
+            and constant.dim() == 2 and constant.size(0) == M and constant.is_contiguous()
+            and constant.is_leaf and constant.requires_grad)
 
 
 def _file_deferred(constant, dpre) -> bool:

@@ -22,8 +22,8 @@ Training (``sharded_train_step``, the trainer's step protgram_directgcn_trainer.
 """
 from __future__ import annotations
 
+import contextlib
 import math
-import weakref
 from dataclasses import dataclass, field
 from typing import List, Optional
 
@@ -32,8 +32,9 @@ import torch.distributed as dist
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, train
 from .graph import CSRGraph, take
+from .layer import Bf16InputCache
 
 # Run the node-range partition's collectives (all-gather, reduce-scatter, all-reduce) even at world size 1, where they
 # are identities: lets a one-GPU box execute the RCCL code paths the 8-GPU run takes (tests/test_gpu_rccl.py).
@@ -350,6 +351,32 @@ def sharded_train_step(model, part: NodeRangePartition, x_full: torch.Tensor, y_
     return float(tot)
 
 
+def _split_params(model, n: int, make_leaf):
+    """A sharded trainer's parameters: (own, dense, node, flat, params, touched). own[layer][name] = this rank's
+    owned-row leaf of each per-node parameter p (nn.Parameter(make_leaf(p))), node = those leaves; dense = the
+    replicated parameters that require grad; flat = one fp32 buffer for dense's gradients (summed over ranks by one
+    all-reduce); params = what the optimizer steps. touched: the ids of the parameters autograd reached since the
+    trainer last cleared it (host-side hooks, no sync): with l2_lambda == 0 the others are not stepped, as
+    torch.optim.Adam skips parameters whose grad is None in the reference loop. The replicated parameters' autograd
+    graph is the same on every rank, so the local record is the global one."""
+    own, node, node_ids = [], [], set()
+    for conv in model.convs:
+        d = {}
+        for name, p in conv.named_parameters(recurse=False):
+            if _is_node_param(name, p, n):
+                d[name] = nn.Parameter(make_leaf(p), requires_grad=p.requires_grad)
+                node_ids.add(id(p))
+                node.append(d[name])
+        own.append(d)
+    dense = [p for p in model.parameters() if id(p) not in node_ids and p.requires_grad]
+    flat = torch.zeros(sum(p.numel() for p in dense), dtype=torch.float32, device=next(model.parameters()).device)
+    params = dense + [p for p in node if p.requires_grad]
+    touched: set = set()
+    for prm in params:
+        prm.register_post_accumulate_grad_hook(lambda t: touched.add(id(t)))
+    return own, dense, node, flat, params, touched
+
+
 class ShardedTrainer:
     """The reference trainer's full-batch step (``protgram_directgcn_trainer.py:91-100``: zero_grad -> forward ->
     ``nll_loss`` (mean over all N nodes) + ``l2_lambda * sum_p ||p||^2`` -> backward -> Adam step) on P ranks, with
@@ -372,40 +399,14 @@ class ShardedTrainer:
 
     def __init__(self, model, part: NodeRangePartition, lr: float = 1e-3, l2_lambda: float = 1e-7, group=None,
                  optimizer_factory=None, **adam_kw):
-        from . import train
         self.model, self.part, self.group, self.l2_lambda = model, part, group, float(l2_lambda)
-        self.own: List[dict] = []
-        node_leaves, dense = [], []
-        full_of = {}
-        for conv in model.convs:
-            d = {}
-            for name, p in conv.named_parameters(recurse=False):
-                if _is_node_param(name, p, part.n):
-                    leaf = nn.Parameter(p.data[part.r0:part.r1], requires_grad=p.requires_grad)
-                    d[name] = leaf
-                    full_of[id(p)] = leaf
-                    node_leaves.append(leaf)
-            self.own.append(d)
-        for name, p in model.named_parameters():
-            if id(p) not in full_of and p.requires_grad:
-                dense.append(p)
-        self.dense = dense
-        self.node = node_leaves
-        dev = dense[0].device if dense else part.local.rowptr.device
-        self.flat = torch.zeros(sum(p.numel() for p in dense), dtype=torch.float32, device=dev)
-        self.params = dense + [p for p in node_leaves if p.requires_grad]
+        # owned-row leaves that share storage with the model's full per-node parameters
+        self.own, self.dense, self.node, self.flat, self.params, self._touched = _split_params(
+            model, part.n, lambda p: p.data[part.r0:part.r1])
         if optimizer_factory is None:
             self.opt = train.Adam(self.params, lr=lr, **adam_kw)
         else:
             self.opt = optimizer_factory(self.params)
-        self._train = train
-        # which parameters autograd reached this step (host-side hooks, no sync): with l2_lambda == 0 the others are
-        # not stepped, as torch.optim.Adam skips parameters whose grad is None in the reference loop (the flat
-        # buffer gives every replicated parameter a zero grad view). The replicated parameters' autograd graph is the
-        # same on every rank, so the local record is the global one.
-        self._touched: set = set()
-        for prm in self.params:
-            prm.register_post_accumulate_grad_hook(lambda t: self._touched.add(id(t)))
 
     def _grads_into_flat(self):
         off = 0
@@ -416,14 +417,14 @@ class ShardedTrainer:
 
     def step(self, x_full: torch.Tensor, y_local: torch.Tensor) -> torch.Tensor:
         """One step; returns the global loss as a device scalar (call .item() only when the value is needed)."""
-        part, lam, train = self.part, self.l2_lambda, self._train
+        part, lam = self.part, self.l2_lambda
         for p in self.node:
             p.grad = None
         self.flat.zero_()
         self._grads_into_flat()  # autograd accumulates into the flat buffer's views in place
         lp, _ = sharded_forward_train(self.model, part, x_full, self.group, own=self.own)
         nll = -lp.float().gather(1, y_local.view(-1, 1)).sum() / part.n
-        self._touched = set()
+        self._touched.clear()
         nll.backward()
         if lam:  # parameters with no gradient path still get the L2 gradient and are stepped
             for p in self.node:
@@ -447,13 +448,8 @@ class ShardedTrainer:
         if lam and not fold:
             ps = [p for p in self.params if p.grad is not None]
             torch._foreach_add_([p.grad for p in ps], [p.detach() for p in ps], alpha=2.0 * lam)
-        if fold:
-            self.opt._l2_extra = 2.0 * lam
-        try:
+        with self.opt.l2_fold(2.0 * lam) if fold else contextlib.nullcontext():
             self.opt.step()
-        finally:
-            if fold:
-                self.opt._l2_extra = 0.0
         return parts.sum() + lam * l2_rep
 
     @torch.no_grad()
@@ -1438,7 +1434,6 @@ class MiddleTrainer:
 
     def __init__(self, model, mp: MiddlePartition, lr: float = 1e-3, l2_lambda: float = 1e-7, comm=None,
                  optimizer_factory=None, graphs: bool = False, **adam_kw):
-        from . import train
         self.model, self.mp, self.l2_lambda = model, mp, float(l2_lambda)
         self.comm = comm if comm is not None else TorchComm()
         # graphs: after WARM eager steps the whole step (forward, backward, collectives, optimizer) is captured once as
@@ -1448,32 +1443,14 @@ class MiddleTrainer:
         self.graphs = bool(graphs)
         if self.graphs and not getattr(self.comm, "capturable", False):
             raise ValueError("graphs=True needs a comm whose collectives can be captured (comm.capturable)")
-        self._graph = None
-        self._eager_steps = 0
         self.xchg = mp.world > 1 or mp.loopback
-        self.own: List[dict] = []
-        node_ids, dense, node_leaves = set(), [], []
-        rows = mp.own
-        for conv in model.convs:
-            d = {}
-            for name, p in conv.named_parameters(recurse=False):
-                if _is_node_param(name, p, mp.n):
-                    leaf = nn.Parameter(p.detach().index_select(0, rows.to(p.device)).contiguous(),
-                                        requires_grad=p.requires_grad)
-                    d[name] = leaf
-                    node_ids.add(id(p))
-                    node_leaves.append(leaf)
-            self.own.append(d)
-        for name, p in model.named_parameters():
-            if id(p) not in node_ids and p.requires_grad:
-                dense.append(p)
-        self.dense, self.node = dense, node_leaves
-        dev = dense[0].device if dense else mp.own.device
-        self.flat = torch.zeros(sum(p.numel() for p in dense), dtype=torch.float32, device=dev)
-        self.params = dense + [p for p in node_leaves if p.requires_grad]
+        # owned-row leaves in middle-major order: copies of the model's rows mp.own (see sync_model)
+        self.own, self.dense, self.node, self.flat, self.params, self._touched = _split_params(
+            model, mp.n, lambda p: p.detach().index_select(0, mp.own.to(p.device)).contiguous())
+        dense, node_leaves = self.dense, self.node
         # train.Adam over two groups (replicated, per-node): its launches also return each group's L2 value of the
         # pre-update parameters (the loss's two L2 terms, one of them all-reduced), so no separate sums are launched
-        node_req = [p for p in node_leaves if p.requires_grad]
+        node_req = self.params[len(dense):]
         self._sq_groups = None
         if optimizer_factory is None:
             groups = [g for g in ({"params": dense}, {"params": node_req}) if g["params"]]
@@ -1482,10 +1459,11 @@ class MiddleTrainer:
                 self._sq_groups = (0 if dense else None, (1 if dense else 0) if node_req else None)
         else:
             self.opt = optimizer_factory(self.params)
-        self._train = train
-        self._touched: set = set()
-        for prm in self.params:
-            prm.register_post_accumulate_grad_hook(lambda t: self._touched.add(id(t)))
+        self._xb = Bf16InputCache()  # the bf16 mode's copy of x_full (body)
+        # the captured step reads self._x / self._y (the first captured step's tensors) and the cache's buffer in place
+        self._captured = train.CapturedStep(
+            lambda: self._step(self._x, self._y), self.opt, mp.own.device, before_replay=self._before_replay,
+            pinned=[lambda: self._xb.buffer], owner="MiddleTrainer") if self.graphs else None
         middle_transpose(mp)  # setup work, outside the steps
         middle_scatter(mp)
 
@@ -1499,7 +1477,7 @@ class MiddleTrainer:
         model, mp = self.model, self.mp
         h = model._apply_pe(x_full)
         if model.compute_dtype == torch.bfloat16:
-            h = self._bf16_input(h) if h is x_full and not h.requires_grad else h.to(torch.bfloat16)
+            h = self._xb(h) if h is x_full and not h.requires_grad else h.to(torch.bfloat16)
         elif model.compute_dtype != torch.float32:
             raise ValueError("compute_dtype must be torch.float32 or torch.bfloat16")
         X, res_x = h, h.index_select(0, mp.own)
@@ -1538,127 +1516,69 @@ class MiddleTrainer:
         return h_own
 
     def _fused_head(self, h_own: torch.Tensor, y_own: torch.Tensor):
-        """The prediction head's forward and backward in one kernel where it takes the shape (train.HEAD_FUSED; bf16
-        h at F = 256: ops.head_train_bf16, fp32 at F = 128: ops.head_train): the owned rows' nll summed and divided by
-        the global N (weight = own rows / N), the decoder's gradients assigned, h's gradient handed to autograd's
-        backward. Returns the nll (device scalar) or None (the caller runs the framework ops)."""
-        from . import ops
-        train, model, mp = self._train, self.model, self.mp
-        head = model.head_train_args() if train.HEAD_FUSED else None
+        """train.fused_head_backward where a kernel takes the shape (train.HEAD_FUSED): the owned rows' nll summed and
+        divided by the global N (weight = own rows / N). Returns the nll (device scalar) or None (the caller runs
+        the framework ops)."""
+        mp = self.mp
+        head = self.model.head_train_args() if train.HEAD_FUSED else None
         if head is None or not h_own.is_cuda:
             return None
-        W1, b1, W2, b2, p_drop = head
         seed = None
-        if p_drop > 0:  # salted by the rank's first middle, as the layers' seeds
+        if head[4] > 0:  # salted by the rank's first middle, as the layers' seeds
             seed = torch.randint(0, 1 << 62, (1,), device=h_own.device, dtype=torch.int64)
             seed ^= ((mp.m0 + 7) * 0xD1B54A32D192ED03) & ((1 << 62) - 1)
-        w = float(h_own.size(0)) / float(mp.n)
-        if h_own.dtype == torch.bfloat16:
-            r = ops.head_train_bf16(h_own, W1, b1, W2, b2, y_own, w, p_drop, seed)
-        else:
-            r = ops.head_train(h_own, W1, b1, W2, b2, y_own, w, p_drop, seed)
+        r = train.fused_head_backward(head, h_own, y_own, float(h_own.size(0)) / float(mp.n), seed)
         if r is None:
             return None
-        loss, dh, grads = r
-        for prm, gr in zip((W1, b1, W2, b2), grads):
-            if prm.requires_grad:
-                prm.grad = gr
-                self._touched.add(id(prm))
-        torch.autograd.backward(h_own, grad_tensors=dh)
-        return loss
+        self._touched.update(id(prm) for prm in r[1])
+        return r[0]
 
-    WARM = 3
-    _xb = None
-
-    def _bf16_input(self, x: torch.Tensor) -> torch.Tensor:
-        """bf16 copy of a step-invariant input (no PE, no gradient): converted once, and again only when x changes
-        (another tensor, or a new version counter: copy_ and in-place writes bump it), in place, so a captured step
-        reads the refreshed values at the same address (the whole-N conversion was ~25 us of a config-5 rank step)."""
-        c = self._xb
-        if c is not None and c[0]() is x and c[1] == x._version:
-            return c[2]
-        if c is not None and c[2].shape == x.shape and c[2].device == x.device:
-            xb = c[2]
-            xb.copy_(x)
-        else:
-            xb = x.to(torch.bfloat16)
-        self._xb = (weakref.ref(x), x._version, xb)
-        return xb
+    WARM = train.CapturedStep.WARM
+    CHECK = train.CapturedStep.CHECK  # train.check_deferred before the first replay of every capture
+    # the captured step's state (train.CapturedStep), None / 0 without graphs
+    _graph = property(lambda self: self._captured and self._captured._graph)
+    failed = property(lambda self: self._captured and self._captured.failed)
+    captures = property(lambda self: self._captured.captures if self._captured else 0)
 
     def step(self, x_full: torch.Tensor, y_own: torch.Tensor) -> torch.Tensor:
         """One step; y_own = the labels of the owned rows (y[mp.own]). Returns the global loss (device scalar; with
         graphs, the graph's static output, overwritten by the next step)."""
         if not self.graphs:
             return self._step(x_full, y_own)
-        if self._graph is None:
-            if self._eager_steps < self.WARM:  # allocator pools, Adam state, descriptor lists, index checks
-                self._eager_steps += 1
-                return self._step(x_full, y_own)
-            self._capture(x_full, y_own)  # replays once: this step
-            return self._loss
+        c = self._captured
+        c.WARM, c.CHECK = self.WARM, self.CHECK
+        if not c.captured:  # eager warm-up steps and the capture run on the caller's tensors
+            self._x, self._y = x_full, y_own
+        self._new = (x_full, y_own)
+        return c()
+
+    def _before_replay(self):
+        x_full, y_own = self._new
         if x_full is not self._x:
             self._x.copy_(x_full)
         if y_own is not self._y:
             self._y.copy_(y_own)
-        if self._xb is not None:
-            self._bf16_input(self._x)  # refreshed outside the graph when x changed (no-op otherwise)
-        # train.Adam's lr / weight_decay are device scalars refreshed here, outside the graph, so a schedule that
-        # changed the learning rate since the last replay (train.fit's ReduceLROnPlateau) takes effect now; another
-        # optimizer whose settings changed is captured again
-        if not self._train.replay_ready(self.opt, self._snap):
-            torch.cuda.synchronize()
-            self._graph = self._keep = None
-            self._capture(self._x, self._y)
-            return self._loss
-        self._graph.replay()
-        return self._loss
+        if self._xb.buffer is not None:
+            self._xb(self._x)  # refreshed outside the graph when x changed (no-op otherwise)
 
     def close(self):
         """Release the captured step (its graph holds RCCL kernels of this process group's communicator): call before
         destroy_process_group. Later steps run eagerly again until the next capture."""
-        torch.cuda.synchronize()
-        self._graph = None
-        self._keep = None
-        self._eager_steps = 0
-
-    CHECK = True  # train.check_deferred before the first replay of every capture
-
-    def _capture(self, x_full, y_own):
-        self._x, self._y = x_full, y_own
-        if isinstance(self.opt, self._train.Adam):
-            self.opt.refresh_hyper()
-        self._train.prepare_capture(x_full.device)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._loss = self._step(self._x, self._y)
-        # everything the captured launches read by address stays alive with the graph: Adam's and the L2 sum's
-        # device descriptor lists (and their pinned staging copies, which captured uploads re-read)
-        self._keep = (list(getattr(self.opt, "_tl_cache", {}).values()) + list(self._train._LISTS.values()) +
-                      self._train.flush_deferred())
-        if self.CHECK:  # every table written after the capture reads back, every address in it is a live block
-            self._train.check_deferred(self._keep)
-        self._graph, self._snap = g, self._train.hyper_snapshot(self.opt)
-        g.replay()  # the step the capture recorded
+        if self._captured is not None:
+            self._captured.close()
 
     def _step(self, x_full: torch.Tensor, y_own: torch.Tensor) -> torch.Tensor:
         # bf16 mode with train.Adam: the owned per-node constants' gradients stay the layers' bf16 dpre, read by Adam
         # directly (train.DEFER_CONST_GRAD, as train.train_step: no fp32 copy written by the backward, none copied
         # into a home buffer, half the bytes read by Adam; the same update bits)
-        from . import ops
-        defer = (self._train.DEFER_CONST_GRAD and isinstance(self.opt, self._train.Adam)
+        defer = (train.DEFER_CONST_GRAD and isinstance(self.opt, train.Adam)
                  and self.model.compute_dtype == torch.bfloat16)
-        prev = ops._DEFER_CONST_GRAD
-        ops._DEFER_CONST_GRAD = defer
-        try:
+        with ops.deferring_const_grads(defer):
             return self._step_body(x_full, y_own)
-        finally:
-            ops._DEFER_CONST_GRAD = prev
-            ops._DEFERRED_GRADS.clear()
 
     def _step_body(self, x_full: torch.Tensor, y_own: torch.Tensor) -> torch.Tensor:
-        from .ops import deferred_grad
-        mp, lam, train = self.mp, self.l2_lambda, self._train
+        deferred_grad = ops.deferred_grad
+        mp, lam = self.mp, self.l2_lambda
         # autograd assigns each parameter's gradient (no .grad preset: a preset one costs an add kernel per parameter
         # per step, ~0.3 ms at config 5); then one multi-tensor copy moves them into their fixed homes: the flat
         # buffer of the replicated parameters (one all-reduce) and, with graphs, persistent per-node buffers (fixed
@@ -1675,7 +1595,7 @@ class MiddleTrainer:
         for p in self.dense + self.node:
             p.grad = None
         self.flat.zero_()
-        self._touched = set()
+        self._touched.clear()
         h_own = self.body(x_full)
         nll = self._fused_head(h_own, y_own)  # the head in one kernel (config 5: bf16, F = 256)
         if nll is None:
@@ -1714,15 +1634,8 @@ class MiddleTrainer:
         if lam and not fold:
             ps = [p for p in self.params if p.grad is not None]
             torch._foreach_add_([p.grad for p in ps], [p.detach() for p in ps], alpha=2.0 * lam)
-        if fold:
-            self.opt._l2_extra = 2.0 * lam
-            self.opt._want_sqsum = "groups" if fused else False
-        try:
+        with self.opt.l2_fold(2.0 * lam, "groups" if fused else False) if fold else contextlib.nullcontext():
             self.opt.step()
-        finally:
-            if fold:
-                self.opt._l2_extra = 0.0
-                self.opt._want_sqsum = False
         if fused:
             sums = self.opt._last_sqsum_groups
             gd, gn = self._sq_groups

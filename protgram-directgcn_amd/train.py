@@ -17,7 +17,9 @@ Gradients equal the reference step's up to float summation order (tests/test_gpu
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import sys
 from typing import Iterable, List, Optional
 
 import numpy as np
@@ -231,11 +233,27 @@ class Adam(torch.optim.Optimizer):
         # reads the learning rate from there at run time, so a HIP-graph replay of the step follows a schedule that
         # changes group["lr"] between replays (ReduceLROnPlateau, protgram_directgcn_trainer.py:84, :102)
         self._hyper: dict = {}
+        # the L2 fold of one step (l2_fold): inputs read by step(), outputs written by it
+        self._l2_extra, self._want_sqsum = 0.0, False
+        self._last_sqsum, self._last_sqsum_groups = None, None
+
+    @contextlib.contextmanager
+    def l2_fold(self, l2_extra: float, want_sqsum=False):
+        """For the step() calls inside the block: `l2_extra` is added to the weight decay in-kernel (the gradient of an
+        L2 term l2_extra / 2 * sum ||p||^2), and with `want_sqsum` the launches also return sum ||p||^2 of the
+        pre-update parameters in `_last_sqsum` (True; stays None if no launch ran) or one value per parameter group
+        in `_last_sqsum_groups` ("groups"). The outputs are cleared on entry, the inputs reset on exit."""
+        self._l2_extra, self._want_sqsum = float(l2_extra), want_sqsum
+        self._last_sqsum, self._last_sqsum_groups = None, None
+        try:
+            yield self
+        finally:
+            self._l2_extra, self._want_sqsum = 0.0, False
 
     def refresh_hyper(self):
         """Write every group's current ``lr`` / ``weight_decay`` into its device scalars (one fill launch per changed
         value, stream-ordered, no host sync). Eager steps call it themselves; the owner of a captured step calls it
-        before every replay (GraphedTrainStep, shard.MiddleTrainer). betas and eps stay as captured."""
+        before every replay (CapturedStep, through replay_ready). betas and eps stay as captured."""
         if _capturing():
             raise RuntimeError("train.Adam.refresh_hyper inside a HIP-graph capture would bake the values into it")
         for gi, group in enumerate(self.param_groups):
@@ -324,9 +342,7 @@ class Adam(torch.optim.Optimizer):
         grad_scale = getattr(self, "grad_scale", None)
         found_inf = getattr(self, "found_inf", None)
         lib = load_library()
-        # train_step's fused L2 value: per-chunk sums of p^2 (pre-update) from every launch, added at the end
-        # (_want_sqsum == "groups": one value per parameter group, in _last_sqsum_groups)
-        want_sq = getattr(self, "_want_sqsum", False)
+        want_sq = self._want_sqsum  # l2_fold: per-chunk sums of p^2 (pre-update) from every launch, added at the end
         sq_parts = []
         group_parts: List[list] = []
         for gi, group in enumerate(self.param_groups):
@@ -364,7 +380,7 @@ class Adam(torch.optim.Optimizer):
                 check(lib.pg_adam_f32(len(members), ctypes.c_void_p(tl.desc.data_ptr()),
                                       ctypes.c_void_p(tl.chunk_ptr.data_ptr()), tl.nchunks, float(group["lr"]),
                                       float(b1), float(b2), float(group["eps"]),
-                                      float(getattr(self, "_l2_extra", 0.0)),  # added to hyper[1] in-kernel
+                                      float(self._l2_extra),  # added to hyper[1] in-kernel
                                       ctypes.c_void_p(step.data_ptr()),
                                       ctypes.c_void_p(gs.data_ptr()) if gs is not None else None,
                                       ctypes.c_void_p(fi.data_ptr()) if fi is not None else None,
@@ -402,13 +418,36 @@ def train_step(model, data, y: torch.Tensor, optimizer, l2_lambda: float = 0.0, 
     """One step of the reference loop (trainer :91-100, or :129-140 with weight = batch nodes / total nodes).
     Returns the total loss (nll * weight + l2_lambda * sum ||p||^2) as a device scalar."""
     defer = DEFER_CONST_GRAD and isinstance(optimizer, Adam) and not (scaler is not None and scaler.is_enabled())
-    prev = ops._DEFER_CONST_GRAD
-    ops._DEFER_CONST_GRAD = defer
-    try:
+    with ops.deferring_const_grads(defer):
         return _train_step(model, data, y, optimizer, l2_lambda, scaler, weight, autocast)
-    finally:
-        ops._DEFER_CONST_GRAD = prev
-        ops._DEFERRED_GRADS.clear()
+
+
+def fused_head_backward(head, h: torch.Tensor, y: torch.Tensor, weight: float, seed=None, scale=None):
+    """The prediction head's forward and backward in one kernel: ops.head_train_bf16 on a bf16 CUDA h (F = 256,
+    config 5: no widened copy either way), else ops.head_train on h.float() (F = 128). `head` = the model's
+    head_train_args(). The decoder parameters get their .grad assigned and h its gradient (already times `scale`, a
+    GradScaler's device scale) through torch.autograd.backward. Returns (loss, the parameters assigned), or None
+    when no kernel takes the shape (nothing done: the caller runs the framework ops)."""
+    W1, b1, W2, b2, p_drop = head
+    r = None
+    if h.is_cuda and h.dtype == torch.bfloat16:
+        r = ops.head_train_bf16(h, W1, b1, W2, b2, y, weight, p_drop, seed, scale)
+    if r is None and h.is_cuda:
+        # a bf16 h is widened only for a shape the fp32 kernel takes: a refused one costs no conversion launch here
+        takes = load_library().pg_head_train_workspace(h.size(0), h.size(1), W1.size(0), W2.size(0)) >= 0
+        if h.dtype != torch.float32 and not takes:
+            return None
+        h = h.float()
+        r = ops.head_train(h, W1, b1, W2, b2, y, weight, p_drop, seed, scale)
+    if r is None:
+        return None
+    loss, dh, grads = r
+    assigned = [prm for prm in (W1, b1, W2, b2) if prm.requires_grad]
+    for prm, gr in zip((W1, b1, W2, b2), grads):
+        if prm.requires_grad:
+            prm.grad = gr
+    torch.autograd.backward(h, grad_tensors=dh)
+    return loss, assigned
 
 
 def _train_step(model, data, y, optimizer, l2_lambda, scaler, weight, autocast):
@@ -422,29 +461,15 @@ def _train_step(model, data, y, optimizer, l2_lambda, scaler, weight, autocast):
         # gradient (already scaled by the GradScaler's scale) from the kernel, the decoder parameters theirs
         with torch.amp.autocast("cuda", enabled=use_amp):
             h = model.body(data)
-        W1, b1, W2, b2, p_drop = head
-        seed = torch.randint(0, 2 ** 62, (1,), device=h.device, dtype=torch.int64) if p_drop > 0 else None
+        seed = torch.randint(0, 2 ** 62, (1,), device=h.device, dtype=torch.int64) if head[4] > 0 else None
         scale = None
         if scaled:
             scaler.scale(torch.zeros((), device=h.device))  # the scale tensor exists from here on
             scale = scaler._scale
-        # bf16 mode at F = 256 (config 5): the kernel reads the bf16 h and returns its bf16 gradient (no widened copy
-        # either way); else the fp32 kernel on h.float() (F = 128)
-        r = None
-        if h.is_cuda and h.dtype == torch.bfloat16:
-            r = ops.head_train_bf16(h, W1, b1, W2, b2, y, weight, p_drop, seed, scale)
-            hf = h
-        if r is None:
-            hf = h.float()
-            r = ops.head_train(hf, W1, b1, W2, b2, y, weight, p_drop, seed, scale) if hf.is_cuda else None
+        r = fused_head_backward(head, h, y, weight, seed, scale)
         if r is not None:
-            loss, dh, grads = r
-            for prm, gr in zip((W1, b1, W2, b2), grads):
-                if prm.requires_grad:
-                    prm.grad = gr
-            torch.autograd.backward(hf, grad_tensors=dh)
-            return _finish_step(model, params, optimizer, loss, l2_lambda, scaler, scaled, backward=False)
-        lp, _ = model.head(hf, need_emb=False)
+            return _finish_step(model, params, optimizer, r[0], l2_lambda, scaler, scaled, backward=False)
+        lp, _ = model.head(h, need_emb=False)
         loss = nll_mean(lp.float(), y) * weight
     else:
         with torch.amp.autocast("cuda", enabled=use_amp):
@@ -471,20 +496,12 @@ def _finish_step(model, params, optimizer, loss, l2_lambda, scaler, scaled, back
         for p in params:
             if p.grad is None and ops.deferred_grad(p) is None:
                 p.grad = torch.zeros_like(p)
-    if fold:
-        optimizer._l2_extra = 2.0 * l2_lambda
-        optimizer._want_sqsum = fused_sq
-        optimizer._last_sqsum = None
-    try:
+    with optimizer.l2_fold(2.0 * l2_lambda, fused_sq) if fold else contextlib.nullcontext():
         if scaled:
             scaler.step(optimizer)
             scaler.update()
         else:
             optimizer.step()
-    finally:
-        if fold:
-            optimizer._l2_extra = 0.0
-            optimizer._want_sqsum = False
     if fused_sq:
         l2 = optimizer._last_sqsum
         if l2 is None:  # the step did not run the kernel (e.g. GradScaler skipped it on the host): measure it
@@ -512,77 +529,80 @@ def replay_ready(optimizer, snapshot: tuple) -> bool:
     return hyper_snapshot(optimizer) == snapshot
 
 
-class GraphedTrainStep:
-    """train_step(model, data, y, optimizer, l2_lambda, scaler) replayed from a HIP graph: `WARM` eager steps (the
-    caches the step builds on first use: the COO -> CSR conversion and tile plans, Adam's state and descriptor lists,
-    the allocator's pools), then the whole step -- forward, loss, backward, the L2 term and the optimizer launch -- is
-    captured once (torch.cuda.CUDAGraph) and every later call is one graph launch. At config 3 the eager step leaves
-    the GPU idle between the backward's launches (host-side autograd work); the replay does not. Dropout draws fresh
-    masks per replay (the capture registers the default generator's Philox offset). The inputs are static: `data.x`
-    and `y` are read where they were at capture (copy new values into them). Returns the loss as the graph's static
-    device scalar, overwritten by the next call.
+class CapturedStep:
+    """A step callable replayed from a HIP graph. `fn()` runs one whole step on the current stream and returns its
+    loss as a device scalar. The first `WARM` calls run it eagerly (the caches a step builds on first use: CSR
+    conversions and tile plans, Adam's state and descriptor lists, the allocator's pools), the next call captures it
+    once (torch.cuda.CUDAGraph) and every later call is one graph launch that returns the graph's static loss,
+    overwritten by the next call. `captured` tells whether a graph is held, `captures` counts them.
 
-    Learning-rate schedules: with train.Adam the replay reads lr / weight_decay from the optimizer's device scalars,
-    refreshed before every replay, so ReduceLROnPlateau (fit(), trainer :84, :102) acts on the next step exactly as
-    in eager steps; any other optimizer is captured again when one of its settings changes.
+    Before every replay: `before_replay()` (the owner copies new inputs into the captured tensors), then replay_ready
+    -- train.Adam's lr / weight_decay are device scalars refreshed there, outside the graph, so a schedule acts on
+    the next step as in eager steps; any other optimizer whose settings changed is captured again (no new warm-up).
+    `pinned`: callables returning the tensors the captured launches read at a fixed address and that something else
+    owns (the bf16 input cache's buffer). The graph keeps the captured ones alive; if a callable returns another
+    tensor before a replay (the cache replaced its buffer), the step is captured again instead of replayed.
 
     Safety: before the first replay every descriptor table written after the capture is read back and every address
     it holds is checked against the allocator's live blocks (check_deferred; CHECK = False skips it). A step that
-    cannot be captured raises (RuntimeError); with eager_fallback=True it runs eagerly instead and the reason is
-    kept in `failed`."""
+    cannot be captured raises RuntimeError and leaves no capture state behind; with eager_fallback=True it runs
+    eagerly from then on, and the reason is kept in `failed` either way."""
     WARM = 3
     CHECK = True  # check_deferred before the first replay of every capture
 
-    def __init__(self, model, data, y: torch.Tensor, optimizer, l2_lambda: float = 0.0, scaler=None,
-                 weight: float = 1.0, eager_fallback: bool = False):
-        self.args = (model, data, y, optimizer)
-        self.kw = dict(l2_lambda=l2_lambda, scaler=scaler, weight=weight)
-        self._graph, self._loss, self._keep, self._eager = None, None, None, 0
-        self._snap = None
+    def __init__(self, fn, optimizer, device, eager_fallback: bool = False, before_replay=None, pinned=(),
+                 owner: Optional[str] = None):
+        self.fn, self.optimizer, self.device = fn, optimizer, device
         self.eager_fallback = bool(eager_fallback)
+        self.before_replay, self.pinned = before_replay, tuple(pinned)
+        self.owner = owner or type(self).__name__  # names the failure message
+        self._graph, self._loss, self._keep, self._pins, self._snap, self._eager = None, None, None, None, None, 0
         self.failed = None
         self.captures = 0
 
+    @property
+    def captured(self) -> bool:
+        return self._graph is not None
+
     def __call__(self) -> torch.Tensor:
-        if self._graph is not None:
-            if replay_ready(self.args[3], self._snap):
-                model, data = self.args[0], self.args[1]
-                x = getattr(data, "x", None)
-                if getattr(model, "_xb", None) is not None and x is not None:
-                    model.bf16_input(x)  # the bf16 mode's cached input, refreshed outside the graph if x changed
-                self._graph.replay()
-                return self._loss
-            self.close(keep_warm=True)  # a setting the graph baked in changed: capture this step again
+        if self._graph is None:
+            if self.failed is not None or self._eager < self.WARM:
+                self._eager += 1
+                return self.fn()
             return self._capture()
-        if self.failed is not None or self._eager < self.WARM:
-            self._eager += 1
-            return train_step(*self.args, **self.kw)
+        if self.before_replay is not None:
+            self.before_replay()
+        if replay_ready(self.optimizer, self._snap) and all(p() is t for p, t in zip(self.pinned, self._pins)):
+            self._graph.replay()
+            return self._loss
+        self.close(keep_warm=True)  # a setting or an address the graph baked in changed: capture this step again
         return self._capture()
 
     def _capture(self) -> torch.Tensor:
-        import sys
-        opt = self.args[3]
+        opt = self.optimizer
         if isinstance(opt, Adam):
             opt.refresh_hyper()
-        prepare_capture(self.args[2].device)
+        prepare_capture(self.device)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                loss = train_step(*self.args, **self.kw)
+                loss = self.fn()
         except Exception as e:  # noqa: BLE001 -- re-raised unless the caller asked for the eager fallback
             _DEFERRED.clear()
             _CAPTURED_LISTS.clear()
             _ARENA.clear()
             self.failed = repr(e)[:300]
             if not self.eager_fallback:
-                raise RuntimeError(f"GraphedTrainStep: HIP graph capture failed: {self.failed}") from e
-            print(f"[GraphedTrainStep] HIP graph capture failed ({self.failed}); running eager steps", file=sys.stderr)
+                raise RuntimeError(f"{self.owner}: HIP graph capture failed: {self.failed}") from e
+            print(f"[{self.owner}] HIP graph capture failed ({self.failed}); running eager steps", file=sys.stderr)
             torch.cuda.synchronize()
-            return train_step(*self.args, **self.kw)
-        # the descriptor lists the captured launches read by address (and their pinned staging copies, which the
-        # captured uploads re-read) live as long as the graph
-        self._keep = list(getattr(opt, "_tl_cache", {}).values()) + list(_LISTS.values()) + flush_deferred()
+            return self.fn()
+        # what the captured launches read by address lives as long as the graph: the descriptor lists (and their
+        # pinned staging copies, which the captured uploads re-read) and the pinned buffers
+        self._pins = [p() for p in self.pinned]
+        self._keep = (list(getattr(opt, "_tl_cache", {}).values()) + list(_LISTS.values()) + flush_deferred()
+                      + self._pins)
         if self.CHECK:
             check_deferred(self._keep)
         self._graph, self._loss, self._snap = g, loss, hyper_snapshot(opt)
@@ -593,9 +613,32 @@ class GraphedTrainStep:
     def close(self, keep_warm: bool = False):
         """Drop the graph (later calls capture again, after WARM eager steps unless keep_warm)."""
         torch.cuda.synchronize()
-        self._graph, self._loss, self._keep = None, None, None
+        self._graph, self._loss, self._keep, self._pins = None, None, None, None
         if not keep_warm:
             self._eager = 0
+
+
+class GraphedTrainStep(CapturedStep):
+    """train_step(model, data, y, optimizer, l2_lambda, scaler) as a CapturedStep: the whole step -- forward, loss,
+    backward, the L2 term and the optimizer launch -- is one graph launch. At config 3 the eager step leaves the GPU
+    idle between the backward's launches (host-side autograd work); the replay does not. Dropout draws fresh masks
+    per replay (the capture registers the default generator's Philox offset). The inputs are static: `data.x` and `y`
+    are read where they were at capture (copy new values into them); the bf16 mode's cached input
+    (ProtGramDirectGCN.bf16_input) is refreshed before each replay and pinned."""
+
+    def __init__(self, model, data, y: torch.Tensor, optimizer, l2_lambda: float = 0.0, scaler=None,
+                 weight: float = 1.0, eager_fallback: bool = False):
+        self.args = (model, data, y, optimizer)
+        self.kw = dict(l2_lambda=l2_lambda, scaler=scaler, weight=weight)
+        cache = getattr(model, "_xb", None)  # layer.Bf16InputCache
+
+        def refresh():
+            x = getattr(data, "x", None)
+            if cache is not None and cache.buffer is not None and x is not None:
+                model.bf16_input(x)  # outside the graph, in place, if x changed
+
+        super().__init__(lambda: train_step(*self.args, **self.kw), optimizer, y.device, eager_fallback, refresh,
+                         pinned=[lambda: cache.buffer] if cache is not None else ())
 
 
 class EarlyStopper:

@@ -333,6 +333,52 @@ def test_middle_trainer_bf16_deferred_constant_grads_bit_identical(pkg, cuda, gr
     assert all(torch.equal(a, b) for a, b in zip(res[0][1], res[1][1]))
 
 
+def test_middle_trainer_capture_failure_is_clean(pkg, cuda):
+    """A MiddleTrainer step that cannot be captured (a host sync inside the optimizer's step: a Python exception at
+    capture, no device fault) raises train.CapturedStep's RuntimeError, records the reason in `failed` and leaves the
+    capture's module state (train._DEFERRED, _CAPTURED_LISTS, _ARENA) empty: a fresh GraphedTrainStep in the same
+    process then captures and replays, its losses equal to eager steps bit for bit."""
+    from protgram_directgcn_amd import shard, train
+    from test_gpu_configs import _labels, _model
+    n, dims = 3, [64, 64, 64]
+    N, s_, d, c = pkg.synth.de_bruijn_edges(n)
+    g = pkg.build_propagation_csr(N, s_, d, c, device=cuda)
+    x = torch.randn(N, dims[0], generator=torch.Generator().manual_seed(5)).to(cuda)
+    y = _labels(N, n).to(cuda)
+    mp_ = shard.middle_partition(g, 0, 2)
+
+    class SyncingOpt(torch.optim.SGD):  # a host sync in the step: not capturable
+        def step(self, closure=None):
+            float(self.param_groups[0]["params"][0].sum())
+            return super().step(closure)
+
+    m = _model(pkg, dims, N, n).to(cuda).eval()
+    tr = shard.MiddleTrainer(m, mp_, l2_lambda=1e-3, comm=_NoComm(), graphs=True,
+                             optimizer_factory=lambda ps: SyncingOpt(ps, lr=1e-3))
+    yo = y[mp_.own]
+    for _ in range(tr.WARM):
+        tr.step(x, yo)
+    assert tr.failed is None and tr.captures == 0
+    with pytest.raises(RuntimeError, match="capture failed"):
+        tr.step(x, yo)
+    torch.cuda.synchronize()
+    assert tr.failed is not None and tr._graph is None and tr.captures == 0
+    assert not train._DEFERRED and not train._CAPTURED_LISTS and not train._ARENA
+    tr.close()
+    runs = []
+    data = pkg.Data(x=x, graph=g)
+    for graphed in (False, True):
+        m = _model(pkg, dims, N, n).to(cuda).eval()
+        opt = torch.optim.SGD(m.parameters(), lr=1e-2)  # its L2 table is built inside the capture, in the arena
+        st = train.GraphedTrainStep(m, data, y, opt, l2_lambda=1e-3) if graphed else (
+            lambda: train.train_step(m, data, y, opt, l2_lambda=1e-3))  # noqa: E731
+        runs.append([float(st()) for _ in range(train.GraphedTrainStep.WARM + 2)])
+        if graphed:
+            assert st._graph is not None and st.failed is None and st.captures == 1
+            st.close()
+    assert runs[0] == runs[1], runs
+
+
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("bf16", [False, True])
 def test_middle_trainer_fused_dropout_matches_masked(pkg, cuda, bf16, monkeypatch):

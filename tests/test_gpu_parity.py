@@ -1164,6 +1164,48 @@ def test_graphed_train_step_bf16_input_refresh(pkg, cuda):
         assert torch.equal(runs[1][1][k], v), k
 
 
+def test_captured_step_keeps_its_bf16_input(pkg, cuda):
+    """a captured bf16 step reads the model's cached bf16 input by address. A call of
+    model.bf16_input on an input of another shape between replays (embedding another level, a validation graph)
+    replaces the cache's buffer; train.CapturedStep pins the captured buffer and, finding it replaced, captures the
+    step again instead of replaying over freed memory. Warm-up + capture, the foreign call, new values copied into
+    data.x, two more steps: losses and parameters equal eager steps given the same calls, bit for bit."""
+    from protgram_directgcn_amd import train
+    N, s, d, c = pkg.synth.de_bruijn_edges(3)
+    g = pkg.build_propagation_csr(N, s, d, c, device=cuda)
+    x0 = torch.randn(N, 64, generator=torch.Generator().manual_seed(1234)).to(cuda)
+    x1 = torch.randn(N, 64, generator=torch.Generator().manual_seed(99)).to(cuda)
+    other = torch.randn(400, 64, generator=torch.Generator().manual_seed(7)).to(cuda)  # a 2-gram graph's input
+    y = (torch.arange(N, device=cuda) // 400) % 20
+    runs = []
+    for graphed in (False, True):
+        torch.manual_seed(0)
+        m = pkg.ProtGramDirectGCN([64, 64, 64], N, 20, 3, 0, 512, 0.5, True).to(cuda).eval()
+        m.compute_dtype = torch.bfloat16
+        data = pkg.Data(x=x0.clone(), graph=g)
+        opt = train.Adam(m.parameters(), lr=1e-3)
+        st = train.GraphedTrainStep(m, data, y, opt) if graphed else (
+            lambda: train.train_step(m, data, y, opt))  # noqa: E731
+        losses = [float(st()) for _ in range(train.GraphedTrainStep.WARM + 1)]  # the warm-up and the capture
+        if graphed:
+            assert st._graph is not None
+            first, pinned = st.captures, m.bf16_input(data.x)
+        with torch.no_grad():
+            assert m.bf16_input(other).shape == other.shape
+        data.x.copy_(x1)
+        losses += [float(st()) for _ in range(2)]
+        if graphed:
+            print("captures before / after the foreign call:", first, st.captures)
+            assert st._graph is not None and st.captures == first + 1, (first, st.captures)
+            assert m.bf16_input(data.x) is not pinned
+            st.close()
+        runs.append((losses, {k: v.detach().clone() for k, v in m.state_dict().items()}))
+    assert runs[0][0] == runs[1][0], runs
+    assert runs[0][0][-2] != runs[0][0][-3]  # the new input values were read
+    for k, v in runs[0][1].items():
+        assert torch.equal(runs[1][1][k], v), k
+
+
 def test_graphed_train_step_capture_failure_raises(pkg, cuda):
     """a step that cannot be captured (here: a host sync inside it) raises instead of silently
     running eager steps; eager_fallback=True keeps the old behaviour, with the reason in `failed`."""
