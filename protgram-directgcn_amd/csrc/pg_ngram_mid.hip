@@ -408,29 +408,34 @@ __global__ __launch_bounds__(XTHREADS) void ngram_mid_kernel(XP p) {
     // this lane's four accumulator rows i = 16 mw + 4 q4 + r: (k, a) in the out-phase, (k, b) in the in-phase. The
     // padding rows i = 60..63 repeat rows 56..59 (the plan holds their weights twice): their lanes compute the same
     // values and write them to the same places as the lanes of rows 56..59, so no lane needs a branch
-    int rk[4], rv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        int i = 16 * mw + 4 * q4 + r;
-        if (i >= 3 * XK) i -= 4;
-        rk[r] = i / XK;
-        rv[r] = i - rk[r] * XK;
-    }
+    // The four rows never straddle a multiple of K (i = 4 n; K, 2 K and 3 K are multiples of 4): they share k, and
+    // v = v0 + r. Each of the lane's LDS addresses below is therefore one register plus a compile-time offset in r, j
+    // and s. With one register per row and address (16 instead of 4) the plain kernels spilled 4-6 VGPRs at their
+    // 168-VGPR budget and the fp32 one ran 8 us longer per launch at B(20,4), F = 128 (112.5 -> 104.5 us); the mapped
+    // kernel measured the other way round (155.5 -> 161.8 us per launch on the fasta graph) and keeps a register per row
+    int i0 = 16 * mw + 4 * q4;
+    if (i0 >= 3 * XK) i0 -= 4;
+    const int rk0 = i0 / XK, rv0 = i0 - rk0 * XK;
     // LDS byte offsets: sources [row][16 f] (RB-byte rows: 64 fp32, 32 bf16); partial [a][row k K + b][16 f] fp32
     const int src_lane = (q4 * XFC + fl) * ES;               // out: + (b * K + 4 s) * RB
     const int in_lane = (q4 * XCB * XFC + fl) * ES;          // in:  + (4 s * XCB + a) * RB
-    int part_w[4], part_r[4], self_r[4], diag_r[4];
+    constexpr int PSLAB = 3 * XK * 64;  // bytes per a-slab of the partial buffer
+    constexpr bool ROWREG = MAP;
+    constexpr int NR = ROWREG ? 4 : 1;  // registers per address: one per row, or row 0's
+    int part_w_[NR], part_r_[NR], self_r_[NR], diag_r_[NR];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        part_w[r] = LPART + ((rv[r] * 3 * XK + rk[r] * XK + wb) * 16 + fl) * 4;  // out: a = rv, row k K + b; + 2 j * 64
-        part_r[r] = LPART + ((wb * 3 * XK + rk[r] * XK + rv[r]) * 16 + fl) * 4;   // in: + 2 j * 60 * 64
-        self_r[r] = LSELF + ((rv[r] * XK + wb) * XFC + fl) * ES;                  // out: (a = rv, b); + 2 j * RB
-        diag_r[r] = LDIAG + ((rv[r] * XK + wb) * 3 + rk[r]) * 4;                   // + 2 j * 12
-        part_w[r] = opaque(part_w[r]);
-        part_r[r] = opaque(part_r[r]);
-        self_r[r] = opaque(self_r[r]);
-        diag_r[r] = opaque(diag_r[r]);
+    for (int r = 0; r < NR; ++r) {
+        const int rv = rv0 + r;
+        part_w_[r] = opaque(LPART + rv * PSLAB + ((rk0 * XK + wb) * 16 + fl) * 4);  // out: a = rv, row k K + b; + 2 j * 64
+        part_r_[r] = opaque(LPART + wb * PSLAB + ((rk0 * XK + rv) * 16 + fl) * 4);   // in: + 2 j * PSLAB
+        self_r_[r] = opaque(LSELF + ((rv * XK + wb) * XFC + fl) * ES);               // out: (a = rv, b); + 2 j * RB
+        diag_r_[r] = opaque(LDIAG + ((rv * XK + wb) * 3 + rk0) * 4);                 // + 2 j * 12
     }
+    // the address of row r (a compile-time r): its register, or row 0's plus r PSLAB, r 64, r K RB, r K 12
+    auto row = [&](const int (&base)[NR], int r, int step) -> int {
+        if constexpr (ROWREG) return base[r];
+        else return base[0] + r * step;
+    };
     // store-out of a finished in-phase tile: lane l writes 16 B = features 4 (l & 3) .. + 3 of tile row l >> 2
     const int so_i = 16 * mw + (lane >> 2) - (16 * mw + (lane >> 2) >= 3 * XK ? 4 : 0);  // padding rows: as above
     const int so_k = so_i / XK, so_b = so_i - so_k * XK;
@@ -466,10 +471,10 @@ __global__ __launch_bounds__(XTHREADS) void ngram_mid_kernel(XP p) {
             float w0[4], w1[4], s0[4], s1[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                w0[r] = *reinterpret_cast<const float*>(L + diag_r[r] + 2 * j * 12);
-                w1[r] = *reinterpret_cast<const float*>(L + diag_r[r] + (2 * j + 2) * 12);
-                s0[r] = lds_src<BF>(L + self_r[r] + 2 * j * RB);
-                s1[r] = lds_src<BF>(L + self_r[r] + (2 * j + 2) * RB);
+                w0[r] = *reinterpret_cast<const float*>(L + row(diag_r_, r, XK * 12) + 2 * j * 12);
+                w1[r] = *reinterpret_cast<const float*>(L + row(diag_r_, r, XK * 12) + (2 * j + 2) * 12);
+                s0[r] = lds_src<BF>(L + row(self_r_, r, XK * RB) + 2 * j * RB);
+                s1[r] = lds_src<BF>(L + row(self_r_, r, XK * RB) + (2 * j + 2) * RB);
             }
             asm volatile("" ::: "memory");  // the reads above are issued before the MFMAs below
             f4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -480,8 +485,9 @@ __global__ __launch_bounds__(XTHREADS) void ngram_mid_kernel(XP p) {
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {  // + the diagonal term Wdiag_k[a, b] X[a.M.b, f]
-                *reinterpret_cast<float*>(L + part_w[r] + 2 * j * 64) = __builtin_fmaf(w0[r], s0[r], acc0[r]);
-                *reinterpret_cast<float*>(L + part_w[r] + (2 * j + 2) * 64) = __builtin_fmaf(w1[r], s1[r], acc1[r]);
+                const int pw = row(part_w_, r, PSLAB);
+                *reinterpret_cast<float*>(L + pw + 2 * j * 64) = __builtin_fmaf(w0[r], s0[r], acc0[r]);
+                *reinterpret_cast<float*>(L + pw + (2 * j + 2) * 64) = __builtin_fmaf(w1[r], s1[r], acc1[r]);
             }
             asm volatile("" ::: "memory");
         }
@@ -511,8 +517,8 @@ __global__ __launch_bounds__(XTHREADS) void ngram_mid_kernel(XP p) {
             f4_t acc0, acc1;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                acc0[r] = *reinterpret_cast<const float*>(L + part_r[r] + 2 * j * 3 * XK * 64);
-                acc1[r] = *reinterpret_cast<const float*>(L + part_r[r] + (2 * j + 2) * 3 * XK * 64);
+                acc0[r] = *reinterpret_cast<const float*>(L + row(part_r_, r, 64) + 2 * j * PSLAB);
+                acc1[r] = *reinterpret_cast<const float*>(L + row(part_r_, r, 64) + (2 * j + 2) * PSLAB);
             }
             if (j + 2 < XTPW) rd_in(j + 2, xi[((j >> 1) + 1) & 1]);
             asm volatile("" ::: "memory");  // the reads above are issued before the MFMAs below
@@ -523,8 +529,8 @@ __global__ __launch_bounds__(XTHREADS) void ngram_mid_kernel(XP p) {
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                *reinterpret_cast<float*>(L + part_r[r] + 2 * j * 3 * XK * 64) = acc0[r];
-                *reinterpret_cast<float*>(L + part_r[r] + (2 * j + 2) * 3 * XK * 64) = acc1[r];
+                *reinterpret_cast<float*>(L + row(part_r_, r, 64) + 2 * j * PSLAB) = acc0[r];
+                *reinterpret_cast<float*>(L + row(part_r_, r, 64) + (2 * j + 2) * PSLAB) = acc1[r];
             }
             asm volatile("" ::: "memory");
         }
