@@ -519,6 +519,30 @@ typedef struct pg_adam_desc {
 int pg_adam_f32(int ntens, const pg_adam_desc_t* descs, const int64_t* chunk_ptr, int64_t nchunks, double lr,
                 double beta1, double beta2, double eps, double weight_decay, float* step, const float* grad_scale,
                 const float* found_inf, float* sq_partial, const double* hyper, void* stream);
+
+/* pg_adam_f32 with row-sparse gradients (the clustered trainer, protgram_directgcn_trainer.py:129-140: a step on a
+ * ~500-node subgraph gives gradients to n_c rows of the [N, F] per-node constant and of the [N, 1] gate vectors).
+ * Exact Adam still visits every row -- a zero gradient decays m and v and moves p, and the L2 term touches every
+ * row -- but the dense [N, F] gradient that is zero outside those rows is neither written nor read: a parameter row
+ * whose pos is -1 takes g = 0 through the same arithmetic. Bit-identical to pg_adam_f32 on the dense gradient
+ * zeros.index_copy_(0, rows, g): p, m, v, every sq_partial chunk and the step counter, found_inf and hyper included.
+ * numel must be a multiple of width, 1 <= width <= 2^30, and every pos entry -1 or a row of g. */
+typedef struct pg_adam_rows_desc {
+    float* p;
+    const void* g;
+    float* m;
+    float* v;
+    int64_t numel;
+    int64_t gtype;       /* as pg_adam_desc_t: 0 fp32, 1 bf16 */
+    const int32_t* pos;  /* NULL: g is dense [numel], exactly pg_adam_desc_t. else [numel / width]: the row of the
+                            compact gradient g [n_c, width] that holds this parameter row's gradient, or -1: the row's
+                            gradient is 0 */
+    int64_t width;       /* elements per parameter row (F_out for a constant, 1 for a gate vector) */
+} pg_adam_rows_desc_t;
+
+int pg_adam_rows_f32(int ntens, const pg_adam_rows_desc_t* descs, const int64_t* chunk_ptr, int64_t nchunks, double lr,
+                     double beta1, double beta2, double eps, double weight_decay, float* step, const float* grad_scale,
+                     const float* found_inf, float* sq_partial, const double* hyper, void* stream);
 int pg_multi_sum_f32(int64_t n, const float* x, float* out, void* stream);
 
 /* Training step of the prediction head (decoder_fc -> log_softmax -> nll_loss, protgram_directgcn.py:218-222 and

@@ -146,6 +146,9 @@ SIGNATURES = {
     "pg_multi_axpy_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
     "pg_adam_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                    ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "pg_adam_rows_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, ctypes.c_double, ctypes.c_double,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp]),
     "pg_multi_sum_f32": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp]),
     "pg_dense_grads_layout_f32": (ctypes.c_int, [c_i64, c_i64, ctypes.c_int32, c_vp, c_vp, c_vp, c_vp]),
     "pg_gemm_at_b_workspace": (c_i64, [c_i64, c_i64, c_i64]),

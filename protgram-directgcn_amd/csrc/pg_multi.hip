@@ -7,8 +7,12 @@
 //   pg_multi_axpy_f32  -- y_t += alpha * x_t for every tensor of a list in one launch (the L2 gradient
 //                         2*lambda*p added to p.grad);
 //   pg_adam_f32        -- Adam over the list in one launch, optionally with the L2 value of the pre-update
-//                         parameters as per-chunk partials (pg_multi_sum_f32 adds them in fixed order).
+//                         parameters as per-chunk partials (pg_multi_sum_f32 adds them in fixed order);
+//   pg_adam_rows_f32   -- the same launch for the clustered trainer's steps, whose per-node parameters get gradients
+//                         in n_c of N rows: a compact [n_c, width] gradient and a row map instead of a dense one.
 // A list is a device array of pg_tensor_desc_t; work is split into fixed 16K-element chunks.
+#include <type_traits>
+
 #include "pg_bf16_util.h"
 #include "pg_common.h"
 
@@ -123,10 +127,16 @@ __device__ __forceinline__ float block_sum256(float s) {
     return red[0];
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(int ntens, const pg_adam_desc_t* d, const int64_t* chunk_ptr,
+// DESC = pg_adam_desc_t: the dense gradient g [numel]. DESC = pg_adam_rows_desc_t (pg_adam_rows_f32): the same, or --
+// pos != NULL -- a compact gradient g [n_c, width] and pos [numel / width]: parameter row r reads row pos[r] of g, or
+// takes g = 0 when pos[r] < 0, through the same upd arithmetic (the decay, the moments and the parameter still move:
+// the update equals the dense one on zeros.index_copy_(0, rows, g), without that N x F tensor being written or read).
+template <typename DESC>
+__global__ __launch_bounds__(256) void adam_kernel(int ntens, const DESC* d, const int64_t* chunk_ptr,
                                                    double lr, double beta1, double beta2, float eps, float weight_decay,
                                                    const float* step, const float* grad_scale, const float* found_inf,
                                                    float* sq_partial, const double* hyper, double wd_extra) {
+    constexpr bool ROWS = std::is_same<DESC, pg_adam_rows_desc_t>::value;
     const bool skip = found_inf && found_inf[0] != 0.f;
     if (skip && !sq_partial) return;
     const int64_t b = blockIdx.x;
@@ -136,7 +146,7 @@ __global__ __launch_bounds__(256) void adam_kernel(int ntens, const pg_adam_desc
         if (chunk_ptr[mid] <= b) lo = mid;
         else hi = mid;
     }
-    const pg_adam_desc_t t = d[lo];
+    const DESC t = d[lo];
     if (hyper) {  // the same double arithmetic the host does for the by-value form: bit-identical updates
         lr = hyper[0];
         weight_decay = (float)(hyper[1] + wd_extra);
@@ -164,9 +174,42 @@ __global__ __launch_bounds__(256) void adam_kernel(int ntens, const pg_adam_desc
     const bool gbf = t.gtype == 1;
     const float* gf = static_cast<const float*>(t.g);
     const uint16_t* gb = static_cast<const uint16_t*>(t.g);
-    const bool vec = ((reinterpret_cast<uintptr_t>(t.g) & (gbf ? 7 : 15)) |
-                      ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.m) |
-                        reinterpret_cast<uintptr_t>(t.v)) & 15)) == 0;
+    // row-sparse gradient: element i = chunk offset o of parameter row row0 + (rem0 + o) / width (32-bit division:
+    // o < CHUNK and width <= 2^30); a row may straddle two chunks
+    const int32_t* pos = nullptr;
+    uint32_t width = 1, rem0 = 0;
+    int64_t row0 = 0, nrows = 0;
+    if constexpr (ROWS) {
+        if (t.pos) {
+            pos = t.pos;
+            const int64_t w = t.width > 0 ? t.width : 1;  // (a width outside the contract: nrows = 0, every g is 0)
+            width = (uint32_t)w;
+            nrows = t.width > 0 ? t.numel / w : 0;
+            row0 = beg / w;
+            rem0 = (uint32_t)(beg - row0 * w);
+        }
+    }
+    auto goff = [&](int64_t i) -> int64_t {  // where element i's gradient sits in the compact g; -1: it is 0
+        const uint32_t o = rem0 + (uint32_t)(i - beg);
+        const uint32_t q = o / width;
+        const int64_t row = row0 + q;
+        const int32_t r = row < nrows ? pos[row] : -1;
+        return r < 0 ? -1 : (int64_t)r * width + (o - q * width);
+    };
+    auto gat = [&](int64_t i) { return gbf ? __uint_as_float((uint32_t)gb[i] << 16) : gf[i]; };
+    auto g1 = [&](int64_t i) {
+        if (ROWS && pos) {
+            const int64_t o = goff(i);
+            return o < 0 ? 0.f : gat(o);
+        }
+        return gat(i);
+    };
+    const bool galign = (reinterpret_cast<uintptr_t>(t.g) & (gbf ? 7 : 15)) == 0;
+    const bool pmv = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.m) |
+                       reinterpret_cast<uintptr_t>(t.v)) & 15) == 0;
+    // p / m / v take the 16-B path whatever the compact gradient allows; it joins when its rows are whole float4s
+    const bool vec = pmv && (galign || (ROWS && pos));
+    const bool gvec = galign && (width & 3) == 0;
     int64_t i0 = beg;
     float sq = 0.f;
     if (skip) {  // L2 value only
@@ -201,7 +244,20 @@ __global__ __launch_bounds__(256) void adam_kernel(int ntens, const pg_adam_desc
         for (int64_t k = threadIdx.x; k < n4; k += 256) {
             const int64_t i = beg + 4 * k;
             // (the bf16 gradient keeps the cached load: non-temporal 8-B loads measured 0.62 against 0.58 ms)
-            const float4 g = gbf ? pgbf::unpack4(*reinterpret_cast<const uint2*>(gb + i)) : ld(gf + i);
+            auto g4 = [&](int64_t j) {
+                return gbf ? pgbf::unpack4(*reinterpret_cast<const uint2*>(gb + j)) : ld(gf + j);
+            };
+            float4 g;
+            if (ROWS && pos) {
+                if (gvec) {  // i and width are multiples of 4: the four elements share a row
+                    const int64_t o = goff(i);
+                    g = o < 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : g4(o);
+                } else {
+                    g = make_float4(g1(i), g1(i + 1), g1(i + 2), g1(i + 3));
+                }
+            } else {
+                g = g4(i);
+            }
             float4 p = ld(t.p + i);
             float4 m = ld(t.m + i);
             float4 v = ld(t.v + i);
@@ -219,7 +275,7 @@ __global__ __launch_bounds__(256) void adam_kernel(int ntens, const pg_adam_desc
     for (int64_t i = i0 + threadIdx.x; i < end; i += 256) {
         float p = t.p[i], m = t.m[i], v = t.v[i];
         sq += p * p;
-        upd(gbf ? __uint_as_float((uint32_t)gb[i] << 16) : gf[i], p, m, v);
+        upd(g1(i), p, m, v);
         t.p[i] = p;
         t.m[i] = m;
         t.v[i] = v;
@@ -232,6 +288,24 @@ __global__ __launch_bounds__(256) void adam_kernel(int ntens, const pg_adam_desc
 
 __global__ void adam_step_kernel(float* step, const float* found_inf) {
     if (!(found_inf && found_inf[0] != 0.f)) step[0] += 1.f;
+}
+
+template <typename DESC>
+int adam_launch(const char* name, int ntens, const DESC* descs, const int64_t* chunk_ptr, int64_t nchunks, double lr,
+                double beta1, double beta2, double eps, double weight_decay, float* step, const float* grad_scale,
+                const float* found_inf, float* sq_partial, const double* hyper, void* stream) {
+    PG_REQUIRE(ntens >= 0 && nchunks >= 0 && step, "%s: bad arguments", name);
+    PG_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && lr >= 0 && eps >= 0, "%s: bad hyper-parameters",
+               name);
+    hipStream_t s = (hipStream_t)stream;
+    if (nchunks > 0) {
+        PG_REQUIRE(descs && chunk_ptr, "%s: null pointer", name);
+        hipLaunchKernelGGL(adam_kernel<DESC>, dim3((unsigned)nchunks), dim3(256), 0, s, ntens, descs, chunk_ptr, lr,
+                           beta1, beta2, (float)eps, hyper ? 0.f : (float)weight_decay, (const float*)step, grad_scale,
+                           found_inf, sq_partial, hyper, weight_decay);
+    }
+    hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, s, step, found_inf);
+    return pg::check_launch(name);
 }
 
 }  // namespace
@@ -262,27 +336,26 @@ int pg_multi_axpy_f32(int ntens, const pg_tensor_desc_t* descs, const int64_t* c
     return pg::check_launch("pg_multi_axpy_f32");
 }
 
+int pg_adam_f32(int ntens, const pg_adam_desc_t* descs, const int64_t* chunk_ptr, int64_t nchunks, double lr,
+                double beta1, double beta2, double eps, double weight_decay, float* step, const float* grad_scale,
+                const float* found_inf, float* sq_partial, const double* hyper, void* stream) {
+    return adam_launch("pg_adam_f32", ntens, descs, chunk_ptr, nchunks, lr, beta1, beta2, eps, weight_decay, step,
+                       grad_scale, found_inf, sq_partial, hyper, stream);
+}
+
+int pg_adam_rows_f32(int ntens, const pg_adam_rows_desc_t* descs, const int64_t* chunk_ptr, int64_t nchunks, double lr,
+                     double beta1, double beta2, double eps, double weight_decay, float* step, const float* grad_scale,
+                     const float* found_inf, float* sq_partial, const double* hyper, void* stream) {
+    return adam_launch("pg_adam_rows_f32", ntens, descs, chunk_ptr, nchunks, lr, beta1, beta2, eps, weight_decay, step,
+                       grad_scale, found_inf, sq_partial, hyper, stream);
+}
+
 int pg_multi_sum_f32(int64_t n, const float* x, float* out, void* stream) {
     PG_REQUIRE(n >= 0 && out && (n == 0 || x), "bad arguments");
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, n, x, out);
     return pg::check_launch("pg_multi_sum_f32");
 }
 
-int pg_adam_f32(int ntens, const pg_adam_desc_t* descs, const int64_t* chunk_ptr, int64_t nchunks, double lr,
-                double beta1, double beta2, double eps, double weight_decay, float* step, const float* grad_scale,
-                const float* found_inf, float* sq_partial, const double* hyper, void* stream) {
-    PG_REQUIRE(ntens >= 0 && nchunks >= 0 && step, "bad arguments");
-    PG_REQUIRE(beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && lr >= 0 && eps >= 0, "bad hyper-parameters");
-    hipStream_t s = (hipStream_t)stream;
-    if (nchunks > 0) {
-        PG_REQUIRE(descs && chunk_ptr, "null pointer");
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nchunks), dim3(256), 0, s, ntens, descs, chunk_ptr, lr, beta1, beta2,
-                           (float)eps, hyper ? 0.f : (float)weight_decay, (const float*)step, grad_scale, found_inf,
-                           sq_partial, hyper, weight_decay);
-    }
-    hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, s, step, found_inf);
-    return pg::check_launch("pg_adam_f32");
-}
 
 }  // extern "C"
 

@@ -42,7 +42,10 @@ def _check_rows(rows: torch.Tensor, limit: int):
         lo, hi = int(rows.min()), int(rows.max())
         if lo < 0 or hi >= limit:
             raise IndexError(f"original_indices in [{lo}, {hi}] outside [0, {limit})")
-    if len(_ROWS_OK) > 64:
+    # whether the rows are distinct (a training step may then hand their gradients to train.Adam row-sparse): found
+    # here, once per tensor, so that the backward's lookup is a cache hit
+    ops.rows_distinct(rows)
+    if len(_ROWS_OK) > 1024:  # above the clustered trainer's 500 subgraphs: an epoch re-checks none of them
         _ROWS_OK.clear()
     _ROWS_OK[k] = weakref.ref(rows)
 

@@ -100,9 +100,65 @@ def deferring_const_grads(enabled: bool):
         _DEFERRED_GRADS.clear()
 
 
-def deferred_grad(p: torch.Tensor) -> Optional[torch.Tensor]:
-    """The bf16 gradient a layer backward filed for parameter p in this train_step (None if none)."""
+def deferred_grad(p: torch.Tensor):
+    """What a layer backward filed for parameter p in this train_step (None if none): the bf16 gradient of p's shape,
+    or -- a step on a subgraph (original_indices) -- the row-sparse pair (grad [n_c, width], rows int64 [n_c])."""
     return _DEFERRED_GRADS.get(p.data_ptr()) if _DEFERRED_GRADS else None
+
+
+# Row-sparse gradients (the clustered trainer's per-subgraph step, protgram_directgcn_trainer.py:129-140). With
+# original_indices the layer's per-node parameters -- the [N, F_out] constant and the five [N, 1] gate vectors -- get
+# gradients in the subgraph's n_c ~ 500 rows only. As .grad that is zeros_like(p).index_add_(0, rows, compact): an
+# N x F fp32 tensor allocated, zero-filled, scattered into and read back by Adam to deliver n_c rows. Under the
+# deferral the backward files (compact, rows) here instead and train.Adam reads the compact rows through a row map
+# (pg_adam_rows_f32): the same update bits. index_add_ sums duplicate rows and the row map cannot, so this needs
+# distinct rows: checked once per rows tensor (rows_distinct, called beside layer._check_rows's range check).
+_ROWS_DISTINCT: dict = {}
+
+
+def rows_info(rows: torch.Tensor) -> tuple:
+    """(distinct, lowest, highest) of an index tensor ((True, 0, -1) when empty). Cached per tensor (address, version,
+    shape) with a weak reference to it, as layer._check_rows: a new tensor at a reused address never hits, and the
+    cache keeps no index tensor alive. The cache outlasts an epoch over the clustered trainer's <= 500 subgraphs."""
+    k = (rows.data_ptr(), rows._version, tuple(rows.shape), rows.dtype, str(rows.device))
+    hit = _ROWS_DISTINCT.get(k)
+    if hit is not None and hit[0]() is rows:
+        return hit[1]
+    if rows.numel():
+        info = (int(torch.unique(rows).numel()) == rows.numel(), int(rows.min()), int(rows.max()))
+    else:
+        info = (True, 0, -1)
+    if len(_ROWS_DISTINCT) > 1024:
+        _ROWS_DISTINCT.clear()
+    _ROWS_DISTINCT[k] = (weakref.ref(rows), info)
+    return info
+
+
+def rows_distinct(rows: torch.Tensor) -> bool:
+    """No index occurs twice in `rows` (rows_info, cached per tensor)."""
+    return rows_info(rows)[0]
+
+
+def _rows_fileable(p, rows) -> bool:
+    """The deferral is on and p [N, width] is what train.Adam steps and looks up by address -- a contiguous fp32 leaf
+    that requires grad -- and `rows` are distinct int64 indices on p's device."""
+    return (_DEFER_CONST_GRAD and rows is not None and p is not None and p.dtype == torch.float32 and p.dim() == 2
+            and p.size(1) > 0 and p.is_contiguous() and p.is_leaf and p.requires_grad and rows.dim() == 1
+            and rows.dtype == torch.int64 and rows.device == p.device and rows_distinct(rows))
+
+
+def _file_rows(p, grad: torch.Tensor, rows) -> bool:
+    """File (grad [n_c, width], rows) for parameter p [N, width] if _rows_fileable and grad is fp32 or bf16 with one
+    row per index. False: nothing filed, the caller builds the dense gradient."""
+    if not _rows_fileable(p, rows):
+        return False
+    if not (grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.size(1) == p.size(1)
+            and grad.size(0) == rows.numel() and grad.device == p.device):
+        return False
+    if p.data_ptr() in _DEFERRED_GRADS:
+        raise RuntimeError("a deferred gradient was filed twice for one parameter")
+    _DEFERRED_GRADS[p.data_ptr()] = (grad.contiguous(), rows)
+    return True
 
 
 def _defer_const(constant, need: bool, M: int, rows) -> bool:
@@ -1179,11 +1235,13 @@ class LayerDense(torch.autograd.Function):
         rows = rows if ctx.has_rows else None
         packs, ctx.packs = ctx.packs, None
         defer = _is_bf16(dY) and _defer_const(constant, ctx.needs_input_grad[2], Z.size(0), rows)
+        # a subgraph's step under the deferral: _dense_grads files (the bf16 dpre, rows), so no fp32 copy of dpre either
+        sparse = _is_bf16(dY) and ctx.needs_input_grad[2] and _rows_fileable(constant, rows)
         out = layer_dense_backward(dY, Z, Y, prm, ctx.gate_mode, rows=rows, res_x=res_x, W_res=W_res,
                                    act=ctx.act, slope=ctx.slope, need_dZ=ctx.needs_input_grad[0], packs=packs,
                                    drop_p=ctx.drop_p,
                                    dpre_f32=constant is not None and ctx.needs_input_grad[2]
-                                   and constant.dtype == torch.float32 and not defer)
+                                   and constant.dtype == torch.float32 and not defer and not sparse)
         need_const = ctx.needs_input_grad[2]
         if out is not None and defer and _file_deferred(constant, out["dpre"]):
             need_const = False
@@ -1241,7 +1299,9 @@ def _dense_grads(out, prm, gate_mode, rows, Z, constant, res_x, W_res, need, nee
         if gate_mode == 1:
             g[name] = dgate[q].sum().reshape(v.shape)
         elif rows is not None:
-            g[name] = torch.zeros_like(v).index_add_(0, rows, dgate[q].reshape(-1, *v.shape[1:]))
+            dq = dgate[q].reshape(-1, *v.shape[1:])
+            # under the deferral train.Adam reads the n_c rows through its row map; else the dense [N, 1] gradient
+            g[name] = None if _file_rows(v, dq, rows) else torch.zeros_like(v).index_add_(0, rows, dq)
         elif v.size(0) == M:
             g[name] = dgate[q].reshape(v.shape)
         else:
@@ -1251,9 +1311,13 @@ def _dense_grads(out, prm, gate_mode, rows, Z, constant, res_x, W_res, need, nee
     d_const = None
     if constant is not None and need_const:
         dp = out.get("dpre_f32")  # the bf16 backward's own fp32 copy (the same values as the conversion below)
-        if dp is None or dp.dtype != constant.dtype:
+        if rows is not None and _file_rows(constant, dpre if dp is None else dp, rows):
+            dp = None  # filed as it is (fp32, or the bf16 dpre: gtype 1): no N x F zeros, no index_add_
+        elif dp is None or dp.dtype != constant.dtype:
             dp = dpre.to(constant.dtype)
-        if rows is None and constant.size(0) == M:
+        if dp is None:
+            pass
+        elif rows is None and constant.size(0) == M:
             d_const = dp  # every row of the constant receives exactly its dpre row (no zero-fill + add pass)
         else:
             d_const = torch.zeros_like(constant)

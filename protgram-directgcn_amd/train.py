@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import random
 import sys
 from typing import Iterable, List, Optional
 
@@ -77,8 +78,13 @@ class TensorList:
     """Device descriptors + chunk offsets for a list of fp32 tensor groups: field k of descriptor t is the data
     pointer of fields[k][t]; the last int64 is numel (of fields[0][t])."""
 
-    def __init__(self, *fields: List[torch.Tensor], gtype: bool = False):
-        """gtype: pg_adam_desc_t's trailing gradient-type column (field 1 may then hold bf16 tensors: 1)."""
+    def __init__(self, *fields: List[torch.Tensor], gtype: bool = False, rows: Optional[list] = None):
+        """gtype: pg_adam_desc_t's trailing gradient-type column (field 1 may then hold bf16 tensors: 1).
+        rows (with gtype): pg_adam_rows_desc_t's two further columns, per tensor None (a dense gradient: pos = NULL)
+        or the int32 row map `pos`, whose gradient fields[1][t] is then compact: [n_c, width] for a parameter
+        [N, width]."""
+        if rows is not None and not gtype:
+            raise ValueError("row maps belong to the Adam descriptor (gtype)")
         lib = load_library()
         xs = fields[0]
         if not xs:
@@ -89,16 +95,25 @@ class TensorList:
                 ok = t.dtype == torch.float32 or (gtype and k == 1 and t.dtype == torch.bfloat16)
                 if not ok or not t.is_contiguous() or t.device != dev:
                     raise ValueError("tensors must be contiguous fp32 on one device")
-        desc = np.zeros((len(xs), len(fields) + 1 + int(gtype)), dtype=np.int64)
+        desc = np.zeros((len(xs), len(fields) + 1 + int(gtype) + 2 * int(rows is not None)), dtype=np.int64)
         chunks = np.zeros(len(xs) + 1, dtype=np.int64)
         for i, x in enumerate(xs):
             for k, f in enumerate(fields):
                 desc[i, k] = f[i].data_ptr()
             desc[i, len(fields)] = x.numel()
             if gtype:
-                if any(f[i].numel() != x.numel() for f in fields):
+                pos = rows[i] if rows is not None else None
+                if any(f[i].numel() != x.numel() for k, f in enumerate(fields) if not (k == 1 and pos is not None)):
                     raise ValueError("tensor list fields differ in size")
-                desc[i, -1] = 1 if fields[1][i].dtype == torch.bfloat16 else 0
+                desc[i, len(fields) + 1] = 1 if fields[1][i].dtype == torch.bfloat16 else 0
+                if pos is not None:
+                    g = fields[1][i]
+                    if (x.dim() != 2 or g.dim() != 2 or g.size(1) != x.size(1) or x.size(1) < 1
+                            or pos.dtype != torch.int32 or pos.numel() != x.size(0) or not pos.is_contiguous()
+                            or pos.device != dev):
+                        raise ValueError("a row map needs p [N, width], g [n_c, width] and an int32 pos [N]")
+                    desc[i, len(fields) + 2] = pos.data_ptr()
+                    desc[i, len(fields) + 3] = x.size(1)
             chunks[i + 1] = chunks[i] + lib.pg_multi_chunks(x.numel())
         self.fields = fields  # keep the tensors alive while the descriptors may be in use (dropped when cached)
         self.host = []  # the pinned staging copies (see _upload)
@@ -236,6 +251,30 @@ class Adam(torch.optim.Optimizer):
         # the L2 fold of one step (l2_fold): inputs read by step(), outputs written by it
         self._l2_extra, self._want_sqsum = 0.0, False
         self._last_sqsum, self._last_sqsum_groups = None, None
+        # row-sparse gradients (ops.deferred_grad's (grad, rows) pairs, pg_adam_rows_f32): one int32 row map per
+        # (device, number of parameter rows), -1 everywhere between steps -- not one O(N) map per cluster -- and per
+        # device the sources of its set and reset: 0, 1, 2, ... and -1, -1, ...
+        self._pos: dict = {}
+        self._iota: dict = {}
+
+    def _row_map(self, dev, n: int, rows: torch.Tensor):
+        """The (device, n) row map with pos[rows[i]] = i set by one stream-ordered launch (pg_rows_scatter on 4-byte
+        rows), and the callable whose launch puts those entries back to -1 after the Adam launches that read it."""
+        pos = self._pos.get((dev, n))
+        if pos is None:
+            pos = self._pos[(dev, n)] = torch.full((n, 1), -1, dtype=torch.int32, device=dev)
+        k = rows.numel()
+        src = self._iota.get(dev)
+        if src is None or src[0].size(0) < k:
+            m = max(1024, 1 << max(k - 1, 0).bit_length())
+            src = self._iota[dev] = (torch.arange(m, dtype=torch.int32, device=dev).view(m, 1),
+                                     torch.full((m, 1), -1, dtype=torch.int32, device=dev))
+        distinct, lo, hi = ops.rows_info(rows)
+        if not distinct or lo < 0 or hi >= n:
+            raise IndexError(f"train.Adam: a row-sparse gradient's rows, in [{lo}, {hi}], must be distinct and inside "
+                             f"[0, {n})")
+        ops.rows_scatter(src[0][:k], rows, pos, check_idx=False)
+        return pos, lambda: ops.rows_scatter(src[1][:k], rows, pos, check_idx=False)
 
     @contextlib.contextmanager
     def l2_fold(self, l2_extra: float, want_sqsum=False):
@@ -280,11 +319,13 @@ class Adam(torch.optim.Optimizer):
             raise RuntimeError("train.Adam: lr / weight_decay changed without refresh_hyper() before this capture")
         return ctypes.c_void_p(self._hyper[gi][0].data_ptr())
 
-    def _tensor_list(self, fields) -> TensorList:
+    def _tensor_list(self, fields, rows: Optional[list] = None) -> TensorList:
         key = tuple((t.data_ptr(), t.numel(), t.dtype) for f in fields for t in f)
+        if rows is not None:  # pg_adam_rows_desc_t: the members' row maps (None: a dense gradient)
+            key += tuple(None if r is None else r.data_ptr() for r in rows)
         tl = self._tl_cache.get(key)
         if tl is None:
-            tl = TensorList(*fields, gtype=True)  # pg_adam_desc_t: field 1 (the gradient) may be bf16
+            tl = TensorList(*fields, gtype=True, rows=rows)  # field 1 (the gradient) may be bf16
             if not _capturing():  # a capture's lists keep their tensors (deferred bf16 gradients have no other owner)
                 tl.fields = None  # the descriptors hold addresses only; the key guarantees they are current
             if len(self._tl_cache) >= 16:
@@ -345,50 +386,84 @@ class Adam(torch.optim.Optimizer):
         want_sq = self._want_sqsum  # l2_fold: per-chunk sums of p^2 (pre-update) from every launch, added at the end
         sq_parts = []
         group_parts: List[list] = []
-        for gi, group in enumerate(self.param_groups):
-            group_parts.append([])
-            ps = [p for p in group["params"] if p.grad is not None or ops.deferred_grad(p) is not None]
-            if not ps:
-                continue
-            fresh = None
-            for p in ps:
-                if (p.grad is not None and p.grad.is_sparse) or p.dtype != torch.float32:
-                    raise RuntimeError("train.Adam takes dense fp32 parameters")
-                if p.grad is not None and ops.deferred_grad(p) is not None:
-                    raise RuntimeError("train.Adam: a parameter has both .grad and a deferred bf16 gradient")
-                if p.device != ps[0].device:
-                    raise RuntimeError("train.Adam: the parameters of a group must share one device")
-                st = self.state[p]
-                if not st:
-                    if fresh is None:  # new parameters of this step share one counter
-                        fresh = torch.zeros((), dtype=torch.float32, device=p.device)
-                    st["step"] = fresh
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            b1, b2 = group["betas"]
-            dev = ps[0].device
-            gs = grad_scale.to(dev) if grad_scale is not None else None
-            fi = found_inf.to(dev, dtype=torch.float32) if found_inf is not None else None
-            hyper = self._hyper_ptr(gi, dev)
-            for members, step in self._cohorts(ps):
-                grads = [p.grad.contiguous() if p.grad is not None else ops.deferred_grad(p) for p in members]
-                tl = self._tensor_list((members, grads, [self.state[p]["exp_avg"] for p in members],
-                                        [self.state[p]["exp_avg_sq"] for p in members]))
-                if want_sq:
-                    sq_parts.append(tl.partial[:tl.nchunks])
-                    group_parts[-1].append(tl.partial[:tl.nchunks])
-                check(lib.pg_adam_f32(len(members), ctypes.c_void_p(tl.desc.data_ptr()),
-                                      ctypes.c_void_p(tl.chunk_ptr.data_ptr()), tl.nchunks, float(group["lr"]),
-                                      float(b1), float(b2), float(group["eps"]),
-                                      float(self._l2_extra),  # added to hyper[1] in-kernel
-                                      ctypes.c_void_p(step.data_ptr()),
-                                      ctypes.c_void_p(gs.data_ptr()) if gs is not None else None,
-                                      ctypes.c_void_p(fi.data_ptr()) if fi is not None else None,
-                                      ctypes.c_void_p(tl.partial.data_ptr()) if want_sq else None, hyper,
-                                      _stream(dev)),
-                      "pg_adam_f32")
-            for p in ps:  # written in place by the kernel: let autograd / version-keyed caches see it
-                torch.autograd.graph.increment_version(p)
+        # row-sparse gradients filed in this step (ops.deferred_grad's (grad, rows) pairs): Adam reads them through one
+        # row map per (device, parameter rows), set for this step's rows here and put back to -1 after the launches.
+        # Two different rows tensors in one step: the dense gradients are built instead, as a backward without the
+        # deferral would have (zeros.index_add_)
+        sparse = {id(p): ops.deferred_grad(p) for group in self.param_groups for p in group["params"]
+                  if isinstance(ops.deferred_grad(p), tuple)}
+        dense_of: dict = {}
+        if len({id(r) for _, r in sparse.values()}) > 1:
+            for group in self.param_groups:
+                for p in group["params"]:
+                    if id(p) in sparse:
+                        g, r = sparse.pop(id(p))
+                        dense_of[id(p)] = torch.zeros_like(p).index_add_(0, r, g.to(p.dtype))
+        maps: dict = {}    # (device, parameter rows) -> the row map set for this step
+        resets: list = []
+        try:
+            for gi, group in enumerate(self.param_groups):
+                group_parts.append([])
+                ps = [p for p in group["params"] if p.grad is not None or ops.deferred_grad(p) is not None]
+                if not ps:
+                    continue
+                fresh = None
+                for p in ps:
+                    if (p.grad is not None and p.grad.is_sparse) or p.dtype != torch.float32:
+                        raise RuntimeError("train.Adam takes dense fp32 parameters")
+                    if p.grad is not None and ops.deferred_grad(p) is not None:
+                        raise RuntimeError("train.Adam: a parameter has both .grad and a deferred bf16 gradient")
+                    if p.device != ps[0].device:
+                        raise RuntimeError("train.Adam: the parameters of a group must share one device")
+                    st = self.state[p]
+                    if not st:
+                        if fresh is None:  # new parameters of this step share one counter
+                            fresh = torch.zeros((), dtype=torch.float32, device=p.device)
+                        st["step"] = fresh
+                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                b1, b2 = group["betas"]
+                dev = ps[0].device
+                gs = grad_scale.to(dev) if grad_scale is not None else None
+                fi = found_inf.to(dev, dtype=torch.float32) if found_inf is not None else None
+                hyper = self._hyper_ptr(gi, dev)
+                for members, step in self._cohorts(ps):
+                    grads, rmaps = [], []
+                    for p in members:
+                        if id(p) in sparse:
+                            g, r = sparse[id(p)]
+                            if (dev, p.size(0)) not in maps:
+                                maps[(dev, p.size(0))], undo = self._row_map(dev, p.size(0), r)
+                                resets.append(undo)
+                            grads.append(g)
+                            rmaps.append(maps[(dev, p.size(0))])
+                        else:
+                            grads.append(dense_of[id(p)] if id(p) in dense_of else
+                                         p.grad.contiguous() if p.grad is not None else ops.deferred_grad(p))
+                            rmaps.append(None)
+                    rowwise = any(r is not None for r in rmaps)  # one launch either way: dense members have pos = NULL
+                    tl = self._tensor_list((members, grads, [self.state[p]["exp_avg"] for p in members],
+                                            [self.state[p]["exp_avg_sq"] for p in members]), rmaps if rowwise else None)
+                    if want_sq:
+                        sq_parts.append(tl.partial[:tl.nchunks])
+                        group_parts[-1].append(tl.partial[:tl.nchunks])
+                    adam = lib.pg_adam_rows_f32 if rowwise else lib.pg_adam_f32
+                    check(adam(len(members), ctypes.c_void_p(tl.desc.data_ptr()),
+                               ctypes.c_void_p(tl.chunk_ptr.data_ptr()), tl.nchunks, float(group["lr"]),
+                               float(b1), float(b2), float(group["eps"]),
+                               float(self._l2_extra),  # added to hyper[1] in-kernel
+                               ctypes.c_void_p(step.data_ptr()),
+                               ctypes.c_void_p(gs.data_ptr()) if gs is not None else None,
+                               ctypes.c_void_p(fi.data_ptr()) if fi is not None else None,
+                               ctypes.c_void_p(tl.partial.data_ptr()) if want_sq else None, hyper,
+                               _stream(dev)),
+                          "pg_adam_rows_f32" if rowwise else "pg_adam_f32")
+                for p in ps:  # written in place by the kernel: let autograd / version-keyed caches see it
+                    torch.autograd.graph.increment_version(p)
+        finally:
+            for undo in resets:  # every entry this step set is -1 again, also when a launch raised
+                undo()
+
         def fixed_order_sum(chunks):
             parts = torch.cat(chunks) if len(chunks) > 1 else chunks[0]
             out = torch.empty((), dtype=torch.float32, device=parts.device)
@@ -409,7 +484,10 @@ HEAD_FUSED = True
 
 
 # bf16 mode with train.Adam and no GradScaler: the per-node constants' gradients stay the layers' bf16 dpre, read by
-# Adam directly (ops.deferred_grad; the parameters' .grad stay None in this step); False: fp32 .grad as usual
+# Adam directly (ops.deferred_grad; the parameters' .grad stay None in this step); False: fp32 .grad as usual.
+# Under the same condition a step on a subgraph (original_indices: the clustered trainer) files the n_c gradient rows
+# of the constants and the gate vectors with their row indices, in either precision, and Adam reads them through a
+# row map (pg_adam_rows_f32) instead of N x F gradients that are zero outside those rows; False: the dense .grad
 DEFER_CONST_GRAD = True
 
 
@@ -660,6 +738,29 @@ class EarlyStopper:
         return self.counter >= self.patience
 
 
+def _epoch_loop(epoch_loss, optimizer, epochs, use_lr_scheduler, lr_patience, lr_factor, use_early_stopping,
+                es_patience, es_min_delta, scheduler, on_epoch) -> List[dict]:
+    """The epoch loop fit and fit_clustered share: epoch_loss() runs one epoch and returns its loss as a float (the
+    epoch's one host sync); then the scheduler and the early stopper see that value."""
+    if scheduler is None and use_lr_scheduler:
+        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "min", patience=lr_patience,
+                                                               factor=lr_factor)
+    stopper = EarlyStopper(patience=es_patience, min_delta=es_min_delta) if use_early_stopping else None
+    history = []
+    for epoch in range(1, epochs + 1):
+        lrs = [float(g["lr"]) for g in optimizer.param_groups]
+        value = epoch_loss()
+        history.append(dict(epoch=epoch, loss=value, lr=lrs))
+        if scheduler is not None:
+            scheduler.step(value)
+        if on_epoch is not None:
+            on_epoch(history[-1])
+        if stopper is not None and stopper.early_stop(value):
+            history[-1]["stopped"] = True
+            break
+    return history
+
+
 def fit(step, optimizer, epochs: int, *, use_lr_scheduler: bool = True, lr_patience: int = 10,
         lr_factor: float = 0.5, use_early_stopping: bool = True, es_patience: int = 25, es_min_delta: float = 1e-5,
         scheduler=None, on_epoch=None) -> List[dict]:
@@ -670,21 +771,48 @@ def fit(step, optimizer, epochs: int, *, use_lr_scheduler: bool = True, lr_patie
     'min', the trainer's patience / factor, config.py:77-79) -> early stop on ``loss.item()`` (EarlyStopper, config.py
     :81-83). The defaults are the reference configuration's. `scheduler` replaces the default ReduceLROnPlateau (any
     object with step(metric)). Returns one record per epoch: loss (float) and the learning rates the step used."""
-    if scheduler is None and use_lr_scheduler:
-        scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, "min", patience=lr_patience,
-                                                               factor=lr_factor)
-    stopper = EarlyStopper(patience=es_patience, min_delta=es_min_delta) if use_early_stopping else None
-    history = []
-    for epoch in range(1, epochs + 1):
-        lrs = [float(g["lr"]) for g in optimizer.param_groups]
-        loss = step()
-        value = float(loss)  # the reference's one host sync per epoch (scheduler.step(loss), loss.item())
-        history.append(dict(epoch=epoch, loss=value, lr=lrs))
-        if scheduler is not None:
-            scheduler.step(value)
-        if on_epoch is not None:
-            on_epoch(history[-1])
-        if stopper is not None and stopper.early_stop(value):
-            history[-1]["stopped"] = True
-            break
-    return history
+    # float(loss): the reference's one host sync per epoch (scheduler.step(loss), loss.item())
+    return _epoch_loop(lambda: float(step()), optimizer, epochs, use_lr_scheduler, lr_patience, lr_factor,
+                       use_early_stopping, es_patience, es_min_delta, scheduler, on_epoch)
+
+
+def clustered_step(model, optimizer, l2_lambda: float = 0.0, scaler=None):
+    """The per-cluster step of the reference's clustered trainer (protgram_directgcn_trainer.py:129-140) for
+    fit_clustered: step(sub, weight) = train_step(model, sub, sub.y, optimizer, l2_lambda, scaler, weight), the loss
+    as a device scalar. `sub` is one of cluster.build_subgraphs' Data objects (x, y, graph, original_indices). With
+    train.Adam and no enabled GradScaler the per-node parameters' gradients reach the optimizer row-sparse
+    (pg_adam_rows_f32): no N x F gradient is built for a ~500-node step."""
+
+    def step(sub, weight: float) -> torch.Tensor:
+        return train_step(model, sub, sub.y, optimizer, l2_lambda, scaler, weight)
+
+    return step
+
+
+def fit_clustered(step, subgraphs: list, optimizer, epochs: int, *, total_nodes: int, shuffle=random.shuffle,
+                  use_lr_scheduler: bool = True, lr_patience: int = 10, lr_factor: float = 0.5,
+                  use_early_stopping: bool = True, es_patience: int = 25, es_min_delta: float = 1e-5, scheduler=None,
+                  on_epoch=None) -> List[dict]:
+    """The reference's clustered epoch loop (protgram_directgcn_trainer.py:125-150, its training path for graphs above
+    10,000 nodes) around a per-cluster step callable step(sub, weight) -> loss (clustered_step). Per epoch:
+    ``shuffle(subgraphs)`` in place (the default random.shuffle: under random.seed(s) the reference's visiting order);
+    per cluster one optimizer step with weight = sub.num_nodes / total_nodes (0.0 when total_nodes <= 0, :134); the
+    epoch's loss is the average of the cluster losses (:141-142), which goes to ``scheduler.step`` and the
+    EarlyStopper exactly as fit's loss does. The cluster losses are added in float64 on the device in visiting order
+    and read once per epoch, where the reference syncs per step with loss.item(): a sequential float64 sum of the
+    same fp32 values is the same number either way. Returns fit's records: epoch, the average loss, the learning
+    rates."""
+    if not subgraphs:
+        raise ValueError("fit_clustered needs at least one subgraph")
+
+    def epoch_loss() -> float:
+        shuffle(subgraphs)
+        total = None
+        for sub in subgraphs:
+            weight = sub.num_nodes / total_nodes if total_nodes > 0 else 0.0
+            loss = torch.as_tensor(step(sub, weight)).detach().to(torch.float64)
+            total = loss if total is None else total + loss
+        return float(total) / len(subgraphs)
+
+    return _epoch_loop(epoch_loss, optimizer, epochs, use_lr_scheduler, lr_patience, lr_factor, use_early_stopping,
+                       es_patience, es_min_delta, scheduler, on_epoch)
