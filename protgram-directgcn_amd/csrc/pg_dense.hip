@@ -779,20 +779,27 @@ __global__ __launch_bounds__(512) void dense_x3_kernel(DenseP p) {
 // Software-pipelined split-bf16 W-stationary kernel (the default for F_in = 128, F_out = 128, no row map).
 // Same arithmetic as dense_x3_kernel (identical products and accumulation order per output element, hence
 // bit-identical results), on 16-row tiles so that every stage has its own LDS buffer:
-//   tile t:  LDS-DMA A(t) -> Af[t&1] (iteration t-2) | split(t) -> As[t&1] (iteration t-1) | MFMA(t) (iteration t)
-//            | accumulators -> Es, constant/residual rows -> Cs/Rs (top of t+1) | epilogue(t) (end of t+1)
-// Iteration i: [wait A(i+1)] B1 [Es <- acc(i-1); DMA CR(i-1), A(i+2), G(i+2)] then waves 0-3 run MFMA(i) and then
-// split(i+1) while waves 4-7 (the other wave of each SIMD) run split(i+1) and then MFMA(i), so each SIMD's
-// matrix pipe and its VALU/LDS split work overlap; [wait CR(i-1)] B2 [epilogue(i-1)]. Two barriers per tile.
-// LDS: Af 2 x 24 KB, As 2 x 36 KB, Cs/Rs 16 KB, Es 8.3 KB, gate inputs 4 x 512 B, bias sums 2 KB.
+//   tile t:  LDS-DMA A(t) -> Af[t&1] (iteration t-2) | split(t) -> As[t&1] (iteration t-1) | MFMA(t) and
+//            epilogue(t) from the accumulator registers (iteration t)
+// The MFMAs take W as their first operand and the A unit as their second (both operands have the same lane layout:
+// lane & 15 = row / column, lane >> 4 = k group), so the accumulators hold the transposed tile: lane (lc, kg) of wave
+// w has Y[m0 + lc][16w + 4kg .. 16w + 4kg + 3], one float4 of one output row. The epilogue therefore needs no LDS:
+// Iteration i: [wait A(i+1)] B1 [two global_load_dwordx4: constant and residual of tile i at this lane's row and
+// columns; DMA A(i+2), G(i+2)] then waves 0-3 run MFMA(i), epilogue(i), split(i+1) while waves 4-7 (the other wave of
+// each SIMD) run split(i+1), MFMA(i), epilogue(i), so each SIMD's matrix pipe and its VALU/LDS split work overlap.
+// One barrier per tile. LDS: Af 2 x 24 KB, As 2 x 36 KB, gate inputs 4 x 512 B, bias sums 2 KB.
+// LDSE (PG_FLAG_DENSE_LDS_EPILOGUE): the earlier epilogue, kept for bitwise comparison and A/B timing: MFMA(a, w), a
+// lane's accumulators being four rows of one column, parked in Es at the top of iteration t+1 next to the constant /
+// residual rows (LDS-DMA -> Cs / Rs), a second barrier B2, and epilogue(t) at the end of iteration t+1 reading all
+// three back as float4 (+ 24.8 KB of LDS).
 __device__ __forceinline__ int a_unit16(int s, int r, int g) { return 64 * s + 4 * r + (g ^ ((-(r >> 2)) & 3)); }
 
 // IL (the default; PG_FLAG_DENSE_NO_IL clears it): the A and gate-input LDS-DMA pieces of tile i + 2 are issued between the k-steps of
 // the wave's MFMA phase instead of all at the top of the iteration (stamps: issuing the five or seven pieces at once
-// took ~1,750 of an iteration's ~7,300 cycles, the memory pipeline pushing back); the constant / residual pieces stay
+// took ~1,750 of an iteration's ~7,300 cycles, the memory pipeline pushing back); the constant / residual loads stay
 // first, so the counted vmcnt waits are unchanged.
 // DROP: the fused layer dropout (training); the inference instantiations carry no trace of it.
-template <bool PRE, bool IL, bool DROP>
+template <bool PRE, bool IL, bool DROP, bool LDSE>
 __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     constexpr int F_IN = 128, K = 384;
     constexpr int CH = K / 4;    // fp32 16-B chunks per row
@@ -801,16 +808,16 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     constexpr int BM = 16;       // rows per tile
     constexpr int NI = BM * CH / 64 / 8;  // A-row LDS-DMA pieces per wave per tile (3)
     constexpr int NG = 2;                 // gate-input pieces per tile (wave 0)
-    constexpr int NCR = 2;                // constant + residual pieces per wave per tile
+    constexpr int NCR = 2;                // constant + residual loads (LDSE: LDS-DMA pieces) per wave per tile
     (void)NCR;
-    constexpr int ELD = 128 + 4;
+    [[maybe_unused]] constexpr int ELD = 128 + 4;
     static_assert(BM * CH % 512 == 0 && NI == 3, "tile shape");
     __shared__ __attribute__((aligned(16))) float Af0[BM * K];  // separate objects: the compiler tells the DMA
     __shared__ __attribute__((aligned(16))) float Af1[BM * K];  // target apart from the buffer being read
     __shared__ __attribute__((aligned(16))) uint4 As[2][3][BM * NU];
-    __shared__ __attribute__((aligned(16))) float Cs[BM * 128];
-    __shared__ __attribute__((aligned(16))) float Rs[BM * 128];
-    __shared__ __attribute__((aligned(16))) float Es[BM * ELD];
+    __shared__ __attribute__((aligned(16))) float Cs[LDSE ? BM * 128 : 4];  // LDSE only: the three epilogue buffers
+    __shared__ __attribute__((aligned(16))) float Rs[LDSE ? BM * 128 : 4];  // (never referenced otherwise)
+    __shared__ __attribute__((aligned(16))) float Es[LDSE ? BM * ELD : 4];
     __shared__ __attribute__((aligned(16))) float Gi[4][8][BM];
     __shared__ __attribute__((aligned(16))) float Bs[4][128];
 
@@ -867,7 +874,8 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
             split8(v, w0[s], w1[s], w2[s]);
         }
     }
-    const int ej = tid & 31, er = tid >> 5;  // epilogue: columns [4ej, 4ej+4) of row er
+    // epilogue: columns [ec, ec + 4) of tile row er -- the lane's own accumulators, or (LDSE) a float4 of the Es tile
+    const int ec = LDSE ? 4 * (tid & 31) : 16 * wave + 4 * kg, er = LDSE ? tid >> 5 : lc;
     const bool has_const = p.constant && p.gate_mode == PG_GATES_VECTOR;
     const bool id_res = p.res_x && !p.proj_res;
     auto tile_of = [&](int64_t kt) { return lo + max((int64_t)0, min(kt, ntl - 1)) * step; };
@@ -906,7 +914,39 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
         glds4(cq + r, &Gi[slot][0][0]);
         glds4(c4 + r, &Gi[slot][4][0]);
     };
-    auto issue_CR = [&](int64_t tile) {  // wave w: rows 2w, 2w + 1
+    // constant and residual of this lane's epilogue float4 (row er, columns ec) of a tile: two global_load_dwordx4,
+    // issued at the top of the tile's own iteration and first used after its MFMAs. Always two loads per wave (an
+    // absent operand loads a valid address of the tile's first Z row and is zeroed), so the counted waits hold.
+    // Through inline asm: behind a load it knows of, hipcc waits vmcnt(0) once LDS-DMA is in flight, which would
+    // drain the next-but-one tile's A pieces. cv / rv are therefore undefined until wait_CR (which hands them to the
+    // compiler as its outputs); nothing may touch them in between.
+    [[maybe_unused]] f32x4 cv = {0.f, 0.f, 0.f, 0.f}, rv = cv;
+    [[maybe_unused]] auto load_CR = [&](int64_t tile) {
+        if (DEXP(4)) return;
+        const int64_t m0 = tile * BM;
+        const int rmax = (int)min((int64_t)(BM - 1), p.M - 1 - m0);
+        const int rr = min(er, rmax);
+        const float* cb = has_const ? p.constant + m0 * p.ld_const + (rr * (int)p.ld_const) : p.Z + m0 * p.ldz;
+        const float* rb = !id_res    ? p.Z + m0 * p.ldz
+                          : p.map_res ? p.res_x + ngram_row(p, m0 + rr) * p.ld_res
+                                      : p.res_x + m0 * p.ld_res + (rr * (int)p.ld_res);
+        if (p.nt_a)
+            asm volatile("global_load_dwordx4 %0, %2, off nt\n\tglobal_load_dwordx4 %1, %3, off"
+                         : "=&v"(cv), "=&v"(rv)
+                         : "v"(cb + ec), "v"(rb + ec)
+                         : "memory");
+        else
+            asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx4 %1, %3, off"
+                         : "=&v"(cv), "=&v"(rv)
+                         : "v"(cb + ec), "v"(rb + ec)
+                         : "memory");
+    };
+    // C and R have landed: younger in this wave's queue are the NI A pieces (+ NG gate pieces on wave 0) of tile i + 2
+    [[maybe_unused]] auto wait_CR = [&]() {
+        if (wave == 0) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(cv), "+v"(rv) : "n"(NI + NG) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(cv), "+v"(rv) : "n"(NI) : "memory");
+    };
+    [[maybe_unused]] auto issue_CR = [&](int64_t tile) {  // LDSE: wave w fetches rows 2w, 2w + 1 into Cs / Rs
         if (DEXP(4)) return;
         const int64_t m0 = tile * BM;
         const int rmax = (int)min((int64_t)(BM - 1), p.M - 1 - m0);
@@ -989,12 +1029,21 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
                 op[(s + 1) & 1][2] = a2[64 * (s + 1)];
             }
             const uint4 x0 = op[s & 1][0], x1 = op[s & 1][1], x2 = op[s & 1][2];
-            acc = mfma_bf(x2, w0[s], acc);  // small terms first (the order of dense_x3_kernel)
-            acc = mfma_bf(x1, w1[s], acc);
-            acc = mfma_bf(x0, w2[s], acc);
-            acc = mfma_bf(x1, w0[s], acc);
-            acc = mfma_bf(x0, w1[s], acc);
-            acc = mfma_bf(x0, w0[s], acc);
+            if constexpr (LDSE) {
+                acc = mfma_bf(x2, w0[s], acc);  // small terms first (the order of dense_x3_kernel)
+                acc = mfma_bf(x1, w1[s], acc);
+                acc = mfma_bf(x0, w2[s], acc);
+                acc = mfma_bf(x1, w0[s], acc);
+                acc = mfma_bf(x0, w1[s], acc);
+                acc = mfma_bf(x0, w0[s], acc);
+            } else {  // the same six products, operands swapped: the accumulators hold the transposed tile
+                acc = mfma_bf(w0[s], x2, acc);
+                acc = mfma_bf(w1[s], x1, acc);
+                acc = mfma_bf(w2[s], x0, acc);
+                acc = mfma_bf(w0[s], x1, acc);
+                acc = mfma_bf(w1[s], x0, acc);
+                acc = mfma_bf(w0[s], x0, acc);
+            }
             if constexpr (IL) {
                 if (issue && (s == 2 || s == 5 || s == 8)) issue_A_piece(a_tile, a_dst, s / 3);
                 if (issue && s == 10 && wave == 0) issue_G(a_tile, g_slot);
@@ -1016,78 +1065,133 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     }
     // bias sums of this thread's epilogue columns (Bs was published by the prologue barrier)
     float4 bq[4];
-    if (ntl > 0) lds_ld4x4(&Bs[0][4 * ej], &Bs[1][4 * ej], &Bs[2][4 * ej], &Bs[3][4 * ej], bq);
-    bool y_pending = false;  // the previous epilogue left exactly one Y store per thread in flight
-    for (int64_t i = 0; i <= ntl && ntl > 0; ++i) {
-        const int ab = (int)(i & 1);
-        [[maybe_unused]] const int si = (int)i;
-        DSTAMP(si, 0);
-        if (y_pending) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // A(i+1), G(i+1) have landed
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        lds_barrier();  // B1: A(i+1) and split(i) visible; epilogue(i-2) done with Es / Cs / Rs; As[ab ^ 1] free
-        DSTAMP(si, 1);
-        if (i >= 1) {
+    if (ntl > 0) lds_ld4x4(&Bs[0][ec], &Bs[1][ec], &Bs[2][ec], &Bs[3][ec], bq);
+    // epilogue of tile row er, columns [ec, ec + 4): epi_sum, activation, dropout, one float4 store
+    auto epilogue = [&](int64_t m0, float4 ov, float4 cq, float4 rq, const float (&c)[5]) {
+        if (!has_const) cq = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!id_res) rq = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float cad = c[4] * c[2];
+        const float s0 = cad * c[0], s1 = cad * c[1], s2 = c[4] * c[3];
+        const float o[4] = {ov.x, ov.y, ov.z, ov.w}, C4[4] = {cq.x, cq.y, cq.z, cq.w}, R4[4] = {rq.x, rq.y, rq.z, rq.w};
+        const float B0[4] = {bq[0].x, bq[0].y, bq[0].z, bq[0].w}, B1[4] = {bq[1].x, bq[1].y, bq[1].z, bq[1].w},
+                    B2[4] = {bq[2].x, bq[2].y, bq[2].z, bq[2].w}, BR[4] = {bq[3].x, bq[3].y, bq[3].z, bq[3].w};
+        float y[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) lds_stf(&Es[(4 * kg + e) * ELD + col], acc[e]);
+        for (int e = 0; e < 4; ++e) {
+            const float qv = epi_sum(o[e], s0, s1, s2, B0[e], B1[e], B2[e], BR[e], C4[e], R4[e]);
+            y[e] = (p.act && !(qv > 0.f)) ? qv * p.slope : qv;
+            if (DROP) y[e] = drop_apply(p, dseed, m0 + er, ec + e, y[e]);
         }
-        issue_CR(tile_of(i - 1));
-        const int64_t a_tile = tile_of(i + 2);
-        float* const a_dst = ab ? Af1 : Af0;  // Af[(i + 2) & 1] = Af[ab]: split(i) is done with it
-        const int g_slot = (int)((i + 2) & 3);
-        const bool do_mfma = i < ntl, do_split = i + 1 < ntl;
-        if (!IL || !do_mfma) {  // IL: the MFMA phase issues them (or here, past the last tile)
-            issue_A(a_tile, a_dst);
-            if (wave == 0) issue_G(a_tile, g_slot);
-        }
-        DSTAMP(si, 2);
-        if (mfma_first) {
-            if (do_mfma) mfma_tile(ab, a_tile, a_dst, g_slot, IL);
-            DSTAMP(si, 3);
-            if (do_split) split_tile(ab ? Af0 : Af1, ab ^ 1, (int)((i + 1) & 3));
-        } else {
-            if (do_split) split_tile(ab ? Af0 : Af1, ab ^ 1, (int)((i + 1) & 3));
-            DSTAMP(si, 3);
-            if (do_mfma) mfma_tile(ab, a_tile, a_dst, g_slot, IL);
-        }
-        DSTAMP(si, 4);
-        // CR(i-1) has landed: younger are A(i+2) (+ G(i+2) on wave 0)
-        if (wave == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI + NG) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
-        DSTAMP(si, 5);
-        lds_barrier();  // B2: Es and Cs / Rs visible
-        DSTAMP(si, 6);
-        y_pending = false;
-        if (i >= 1) {
-            const int64_t m0 = tile_of(i - 1) * BM;
-            const int gs = (int)((i - 1) & 3);
-            if (m0 + er < p.M) {
-                float4 cv, rv, ov;
+        const int64_t yr = p.map_y ? ngram_row(p, m0 + er) : m0 + er;
+        *reinterpret_cast<float4*>(p.Y + yr * p.ldy + ec) = make_float4(y[0], y[1], y[2], y[3]);
+    };
+    if constexpr (!LDSE) {
+        // every wave-instruction of the vector-memory queue is counted in issue order: per iteration C, R, then the
+        // NI A pieces (+ NG gate pieces on wave 0) of tile i + 2, then the Y store
+        bool y_pending = false;  // the previous epilogue left exactly one Y store of this wave in flight (wave-uniform)
+        for (int64_t i = 0; i < ntl; ++i) {
+            const int ab = (int)(i & 1);
+            [[maybe_unused]] const int si = (int)i;
+            DSTAMP(si, 0);
+            if (y_pending) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // A(i+1), G(i+1) have landed
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            lds_barrier();  // B1: A(i+1), G(i+1) and split(i) visible; As[ab ^ 1] and Af[ab] free
+            DSTAMP(si, 1);
+            const int64_t m0 = tile_of(i) * BM;
+            load_CR(tile_of(i));
+            __builtin_amdgcn_sched_barrier(0);  // the two loads go out here, not next to their use
+            const int64_t a_tile = tile_of(i + 2);
+            float* const a_dst = ab ? Af1 : Af0;  // Af[(i + 2) & 1] = Af[ab]: split(i) is done with it
+            const int g_slot = (int)((i + 2) & 3);
+            const bool do_split = i + 1 < ntl;
+            if (!IL) {  // IL: the MFMA phase issues them
+                issue_A(a_tile, a_dst);
+                if (wave == 0) issue_G(a_tile, g_slot);
+            }
+            DSTAMP(si, 2);
+            // MFMA(i), then the epilogue straight from the accumulators
+            auto mfma_epi = [&](int pt) {
+                mfma_tile(ab, a_tile, a_dst, g_slot, IL);
+                DSTAMP(si, pt);
+                wait_CR();
+                DSTAMP(si, pt + 1);
                 float c[5];
-                lds_epi<BM * 4>(&Cs[er * 128 + 4 * ej], &Rs[er * 128 + 4 * ej], &Es[er * ELD + 4 * ej], &Gi[gs][0][er],
-                                cv, rv, ov, c);
-                if (!has_const) cv = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!id_res) rv = make_float4(0.f, 0.f, 0.f, 0.f);
-                const float cad = c[4] * c[2];
-                const float s0 = cad * c[0], s1 = cad * c[1], s2 = c[4] * c[3];
-                const float o[4] = {ov.x, ov.y, ov.z, ov.w}, C4[4] = {cv.x, cv.y, cv.z, cv.w},
-                            R4[4] = {rv.x, rv.y, rv.z, rv.w};
-                const float B0[4] = {bq[0].x, bq[0].y, bq[0].z, bq[0].w}, B1[4] = {bq[1].x, bq[1].y, bq[1].z, bq[1].w},
-                            B2[4] = {bq[2].x, bq[2].y, bq[2].z, bq[2].w}, BR[4] = {bq[3].x, bq[3].y, bq[3].z, bq[3].w};
-                float y[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float qv = epi_sum(o[e], s0, s1, s2, B0[e], B1[e], B2[e], BR[e], C4[e], R4[e]);
-                    y[e] = (p.act && !(qv > 0.f)) ? qv * p.slope : qv;
-                    if (DROP) y[e] = drop_apply(p, dseed, m0 + er, 4 * ej + e, y[e]);
+                lds_gates5<BM * 4>(&Gi[(int)(i & 3)][0][er], c);
+                if (!DEXP(2) && m0 + er < p.M) {
+                    epilogue(m0, make_float4(acc[0], acc[1], acc[2], acc[3]), make_float4(cv[0], cv[1], cv[2], cv[3]),
+                             make_float4(rv[0], rv[1], rv[2], rv[3]), c);
                 }
-                if (!DEXP(2)) {
-                    const int64_t yr = p.map_y ? ngram_row(p, m0 + er) : m0 + er;
-                    *reinterpret_cast<float4*>(p.Y + yr * p.ldy + 4 * ej) = make_float4(y[0], y[1], y[2], y[3]);
-                    y_pending = true;
+                DSTAMP(si, pt + 2);
+            };
+            // stamp points: waves 0-3  3 MFMA done, 4 C / R landed, 5 epilogue done, 6 split done
+            //               waves 4-7  3 split done, 4 MFMA done, 5 C / R landed, 6 epilogue done
+            if (mfma_first) {
+                mfma_epi(3);
+                if (do_split) split_tile(ab ? Af0 : Af1, ab ^ 1, (int)((i + 1) & 3));
+                DSTAMP(si, 6);
+            } else {
+                if (do_split) split_tile(ab ? Af0 : Af1, ab ^ 1, (int)((i + 1) & 3));
+                DSTAMP(si, 3);
+                mfma_epi(4);
+            }
+            y_pending = !DEXP(2) && m0 + BM <= p.M;  // a partial tile's store may be skipped: drain instead
+        }
+    } else {
+        bool y_pending = false;  // the previous epilogue left exactly one Y store per thread in flight
+        for (int64_t i = 0; i <= ntl && ntl > 0; ++i) {
+            const int ab = (int)(i & 1);
+            [[maybe_unused]] const int si = (int)i;
+            DSTAMP(si, 0);
+            if (y_pending) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");  // A(i+1), G(i+1) have landed
+            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            lds_barrier();  // B1: A(i+1) and split(i) visible; epilogue(i-2) done with Es / Cs / Rs; As[ab ^ 1] free
+            DSTAMP(si, 1);
+            if (i >= 1) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) lds_stf(&Es[(4 * kg + e) * ELD + col], acc[e]);
+            }
+            issue_CR(tile_of(i - 1));
+            const int64_t a_tile = tile_of(i + 2);
+            float* const a_dst = ab ? Af1 : Af0;  // Af[(i + 2) & 1] = Af[ab]: split(i) is done with it
+            const int g_slot = (int)((i + 2) & 3);
+            const bool do_mfma = i < ntl, do_split = i + 1 < ntl;
+            if (!IL || !do_mfma) {  // IL: the MFMA phase issues them (or here, past the last tile)
+                issue_A(a_tile, a_dst);
+                if (wave == 0) issue_G(a_tile, g_slot);
+            }
+            DSTAMP(si, 2);
+            if (mfma_first) {
+                if (do_mfma) mfma_tile(ab, a_tile, a_dst, g_slot, IL);
+                DSTAMP(si, 3);
+                if (do_split) split_tile(ab ? Af0 : Af1, ab ^ 1, (int)((i + 1) & 3));
+            } else {
+                if (do_split) split_tile(ab ? Af0 : Af1, ab ^ 1, (int)((i + 1) & 3));
+                DSTAMP(si, 3);
+                if (do_mfma) mfma_tile(ab, a_tile, a_dst, g_slot, IL);
+            }
+            DSTAMP(si, 4);
+            // CR(i-1) has landed: younger are A(i+2) (+ G(i+2) on wave 0)
+            if (wave == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI + NG) : "memory");
+            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
+            DSTAMP(si, 5);
+            lds_barrier();  // B2: Es and Cs / Rs visible
+            DSTAMP(si, 6);
+            y_pending = false;
+            if (i >= 1) {
+                const int64_t m0 = tile_of(i - 1) * BM;
+                const int gs = (int)((i - 1) & 3);
+                if (m0 + er < p.M) {
+                    float4 cq, rq, ov;
+                    float c[5];
+                    lds_epi<BM * 4>(&Cs[er * 128 + ec], &Rs[er * 128 + ec], &Es[er * ELD + ec], &Gi[gs][0][er], cq, rq, ov, c);
+                    if (!DEXP(2)) {
+                        epilogue(m0, ov, cq, rq, c);
+                        y_pending = true;
+                    }
                 }
             }
+            DSTAMP(si, 7);
         }
-        DSTAMP(si, 7);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the dummy tiles' DMA must land before the LDS is freed
 }
@@ -1249,16 +1353,17 @@ static int dense_launch(const pg_layer_args_t* a, const float* packed, uint32_t 
             const int64_t T16 = (a->M + 15) / 16;
             const unsigned g16 = (unsigned)(T16 < ncu ? T16 : ncu);
             const bool il = (flags & PG_FLAG_DENSE_NO_IL) == 0;
-            if (p.drop_s != 0.f) {
-                if (p.pregated) hipLaunchKernelGGL((dense_x3p_kernel<true, true, true>), dim3(g16), dim3(512), 0, s, p);
-                else hipLaunchKernelGGL((dense_x3p_kernel<false, true, true>), dim3(g16), dim3(512), 0, s, p);
-            } else if (p.pregated) {
-                if (il) hipLaunchKernelGGL((dense_x3p_kernel<true, true, false>), dim3(g16), dim3(512), 0, s, p);
-                else hipLaunchKernelGGL((dense_x3p_kernel<true, false, false>), dim3(g16), dim3(512), 0, s, p);
-            } else {
-                if (il) hipLaunchKernelGGL((dense_x3p_kernel<false, true, false>), dim3(g16), dim3(512), 0, s, p);
-                else hipLaunchKernelGGL((dense_x3p_kernel<false, false, false>), dim3(g16), dim3(512), 0, s, p);
-            }
+            const bool ldse = (flags & PG_FLAG_DENSE_LDS_EPILOGUE) != 0;
+            const bool drop = p.drop_s != 0.f;  // training: interleaved issue only
+            void (*kern)(DenseP);
+#define PG_X3P_PICK(LDSE)                                                                                  \
+    kern = drop ? (p.pregated ? dense_x3p_kernel<true, true, true, LDSE> : dense_x3p_kernel<false, true, true, LDSE>) \
+           : p.pregated ? (il ? dense_x3p_kernel<true, true, false, LDSE> : dense_x3p_kernel<true, false, false, LDSE>) \
+                        : (il ? dense_x3p_kernel<false, true, false, LDSE> : dense_x3p_kernel<false, false, false, LDSE>)
+            if (ldse) PG_X3P_PICK(true);
+            else PG_X3P_PICK(false);
+#undef PG_X3P_PICK
+            hipLaunchKernelGGL(kern, dim3(g16), dim3(512), 0, s, p);
         } else {
             if (p.rawW)
                 return pg::set_error(PG_ERR_UNSUPPORTED, "pg_directgcn_dense_f32: unpacked weights need the pipelined "

@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """A/B timing of the dense layer kernels in the in-tree library on the bench's layer-1 shape (B(20,n), F = 128,
-vector gates, constant, identity residual): the default (dense_x3p_kernel<.., IL>: interleaved LDS-DMA issue) against
-PG_FLAG_DENSE_NO_IL (all pieces at the top of the iteration), interleaved rounds (min and median per launch, HIP events), and a bit-equality check.
-usage: python tools/dense_ab.py [n=4] [rounds=20] [reps=20]"""
+vector gates, constant, identity residual): the default (dense_x3p_kernel: register epilogue, interleaved LDS-DMA issue)
+against PG_FLAG_DENSE_LDS_EPILOGUE (the earlier epilogue through LDS), PG_FLAG_DENSE_NO_IL (all pieces at the top of the
+iteration) and, with --ref-lib PATH, the default of another build of the library (same C ABI, e.g. the parent
+commit's), interleaved rounds (min and median per launch, HIP events; every variant through the same direct
+pg_directgcn_dense_f32 call), and a bit-equality check.
+usage: python tools/dense_ab.py [n=4] [rounds=20] [reps=20] [--ref-lib=PATH]"""
 import json
 import os
 import sys
@@ -15,9 +18,12 @@ from __graft_entry__ import load_package  # noqa: E402
 
 pkg = load_package()
 from protgram_directgcn_amd import ops  # noqa: E402
-from protgram_directgcn_amd._lib import PG_FLAG_DENSE_NO_IL  # noqa: E402
+import ctypes  # noqa: E402
+
+from protgram_directgcn_amd import _lib  # noqa: E402
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
+ref_lib = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--ref-lib=")), None)
 n = int(args[0]) if args else 4
 rounds = int(args[1]) if len(args) > 1 else 20
 reps = int(args[2]) if len(args) > 2 else 20
@@ -32,30 +38,51 @@ x = torch.randn(N, 128, generator=torch.Generator().manual_seed(1234)).to(dev)
 prm = dict(zip(ops._DENSE_KEYS, (p.detach() for p in layer._dense_params())))
 Z = ops.spmm3(g, x)
 Y = torch.empty(N, 128, device=dev)
+a, keep = ops._layer_args(Z, prm, 0, None, layer.constant.detach(), x, None, True, ops.LEAKY_SLOPE)
+a.Y, a.ldy = ops._p(Y), Y.stride(0)
+raw = [ops._f32c(prm[k].detach()) for k in ops._PACK_KEYS]
+(a.W_main_in, a.W_main_out, a.W_undirected, a.W_shared, a.b_main_in, a.b_dir_shared_in, a.b_main_out,
+ a.b_dir_shared_out, a.b_undirected, a.b_undirected_shared) = [ops._p(t) for t in raw]
+st = ops._stream(Z)
+
+
+def entry(lib):
+    fn = lib.pg_directgcn_dense_f32
+    fn.restype, fn.argtypes = _lib.SIGNATURES["pg_directgcn_dense_f32"]
+    return fn
+
+
+own = entry(ctypes.CDLL(pkg.library_path()))
 base = ops.default_flags()
-variants = {"x3p_il": base, "x3p_no_il": base | PG_FLAG_DENSE_NO_IL}
+variants = {"x3p_reg_epilogue": (own, base), "x3p_lds_epilogue": (own, base | _lib.PG_FLAG_DENSE_LDS_EPILOGUE),
+            "x3p_reg_epilogue_no_il": (own, base | _lib.PG_FLAG_DENSE_NO_IL)}
+if ref_lib:
+    variants["ref_lib_default"] = (entry(ctypes.CDLL(os.path.abspath(ref_lib))), base)
 
 
-def run(fl):
-    return ops.layer_dense(Z, prm, 0, constant=layer.constant.detach(), res_x=x, act=True, flags=fl, out=Y)
+def run(v):
+    fn, fl = v
+    rc = fn(ctypes.byref(a), None, fl, st)
+    assert rc == 0, rc
+    return Y
 
 
 with torch.no_grad():
-    outs = {k: run(fl).clone() for k, fl in variants.items()}
-    same = all(torch.equal(outs["x3p_il"], v) for v in outs.values())
+    outs = {k: run(v).clone() for k, v in variants.items()}
+    same = all(torch.equal(outs["x3p_reg_epilogue"], v) for v in outs.values())
     times = {k: [] for k in variants}
     for _ in range(rounds):
-        for k, fl in variants.items():
+        for k, v in variants.items():
             for _ in range(3):
-                run(fl)
+                run(v)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(reps):
-                run(fl)
+                run(v)
             e1.record()
             torch.cuda.synchronize()
             times[k].append(e0.elapsed_time(e1) / reps * 1e3)
 res = {k: {"min_us": round(min(v), 2), "median_us": round(sorted(v)[len(v) // 2], 2)} for k, v in times.items()}
 res["bit_identical"] = same
-res["shape"] = f"B(20,{n}) M={N} F=128, vector gates, constant, identity residual (layer_dense calls incl. host)"
+res["shape"] = f"B(20,{n}) M={N} F=128, vector gates, constant, identity residual (direct C-ABI calls)"
 print(json.dumps(res))

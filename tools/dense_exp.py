@@ -3,6 +3,8 @@
 with -DPG_DENSE_EXP (flag bits 24..28 skip phases: 1 MFMAs, 2 split, 4 Y stores, 8 A DMA, 16 constant / residual DMA;
 results are garbage in those runs), and times the bench's layer-1 dense launch at B(20,n), F=128 with each set of
 phases skipped (min of interleaved rounds, HIP events).
+--stamps: per-iteration cycle stamps of waves 0 and 4 instead; --lds-epilogue: the earlier epilogue through LDS
+(PG_FLAG_DENSE_LDS_EPILOGUE); --no-il: PG_FLAG_DENSE_NO_IL.
 usage: python tools/dense_exp.py --build (in the container), then python tools/dense_exp.py [n=4] [reps=20]"""
 import ctypes
 import json
@@ -15,7 +17,7 @@ SO = os.path.join(REPO, "tools", "libdense_exp.so")
 if "--build" in sys.argv:
     src = os.path.join(REPO, "protgram-directgcn_amd", "csrc")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                           "-DPG_DENSE_EXP", f"-I{REPO}/include", f"-I{src}", os.path.join(src, "pg_dense.hip"),
+                           "-fno-slp-vectorize", "-DPG_DENSE_EXP", f"-I{REPO}/include", f"-I{src}", os.path.join(src, "pg_dense.hip"),
                            os.path.join(src, "pg_abi.cpp"), "-o", SO])
     print("built", SO)
     sys.exit(0)
@@ -53,7 +55,9 @@ a.Y, a.ldy = ops._p(Y), Y.stride(0)
 raw = [ops._f32c(prm[k].detach()) for k in ops._PACK_KEYS]
 (a.W_main_in, a.W_main_out, a.W_undirected, a.W_shared, a.b_main_in, a.b_dir_shared_in, a.b_main_out,
  a.b_dir_shared_out, a.b_undirected, a.b_undirected_shared) = [ops._p(t) for t in raw]
-base = (_lib.PG_FLAG_DENSE_PREGATED if pregated else 0) | (_lib.PG_FLAG_DENSE_NO_IL if "--no-il" in sys.argv else 0)
+LDSE = "--lds-epilogue" in sys.argv
+base = ((_lib.PG_FLAG_DENSE_PREGATED if pregated else 0) | (_lib.PG_FLAG_DENSE_NO_IL if "--no-il" in sys.argv else 0)
+        | (_lib.PG_FLAG_DENSE_LDS_EPILOGUE if LDSE else 0))
 st = ops._stream(Z)
 
 
@@ -88,26 +92,21 @@ if "--stamps" in sys.argv:  # per-iteration cycle breakdown of waves 0 (MFMA fir
     torch.cuda.synchronize()
     lib.pg_dense_set_stamps(None)
     t = buf.view(NB, 2, NIT, NPT).cpu().numpy().astype(np.float64)
-    names = ["wait_A+B1", "issue_dma", "first_phase", "second_phase", "wait_CR", "B2", "epilogue", "to_next_top"]
+    # phases between consecutive stamp points (pg_dense.hip, DSTAMP), per wave kind
+    if LDSE:
+        names = {w: ["wait_A+B1", "issue_dma", "first_phase", "second_phase", "wait_CR", "B2", "epilogue"] for w in (0, 1)}
+    else:
+        names = {0: ["wait_A+B1", "issue_loads", "mfma", "wait_CR", "epilogue", "split"],
+                 1: ["wait_A+B1", "issue_loads", "split", "mfma", "wait_CR", "epilogue"]}
     res = {}
     for w, wn in ((0, "wave0_mfma_first"), (1, "wave4_split_first")):
-        seg = {}
         v = t[:, w]
         its = slice(2, 36)
-        for k in range(NPT - 1):
-            d = v[:, its, k + 1] - v[:, its, k]
-            seg[names[k + 1 if k else 0]] = float(np.median(d))
-        seg["wait_A+B1"] = float(np.median(v[:, its, 1] - v[:, its, 0]))
-        seg["issue_dma"] = float(np.median(v[:, its, 2] - v[:, its, 1]))
-        seg["first_phase"] = float(np.median(v[:, its, 3] - v[:, its, 2]))
-        seg["second_phase"] = float(np.median(v[:, its, 4] - v[:, its, 3]))
-        seg["wait_CR"] = float(np.median(v[:, its, 5] - v[:, its, 4]))
-        seg["B2"] = float(np.median(v[:, its, 6] - v[:, its, 5]))
-        seg["epilogue"] = float(np.median(v[:, its, 7] - v[:, its, 6]))
+        seg = {nm: float(np.median(v[:, its, k + 1] - v[:, its, k])) for k, nm in enumerate(names[w])}
         seg["iteration"] = float(np.median(v[:, 3:37, 0] - v[:, 2:36, 0]))
         res[wn] = {k: round(x, 1) for k, x in seg.items()}
     print("stamps (median cycles per iteration, s_memtime ticks, iterations 2..35 of blocks 0..63):",
-          json.dumps(res) if "json" in globals() else res)
+          json.dumps(res))
     sys.exit(0)
 
 run(0)
