@@ -478,6 +478,36 @@ int pg_directgcn_head_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uin
 int pg_ngram_keys(int64_t nseq, const int64_t* offsets, const uint8_t* bytes, const int32_t* lut, int n,
                   int64_t K, int64_t* keys, int64_t* next_keys, void* stream);
 
+/* ---- protein-level pooling (protgram_directgcn_trainer.py:387-398, "Step 3: Pooling N-gram Embeddings to
+ * Protein Level") ---------------------------------------------------------------------------------------------
+ * Node id of every window: the ngram_map.get("".join(seq[i:i + n])) of models_utils.py:202 and :238-239. For
+ * sequence s and p in [offsets[s], offsets[s+1]): ids[p] = the id of the window [p, p+n) if it lies inside the
+ * sequence, every byte has a code (lut[b] in [0, K); -1 = not in the level's alphabet) and its key (as
+ * pg_ngram_keys) is a node; else -1. The id is the key's position in node_keys (sorted, [N]) by binary search, or
+ * table[key] when `table` ([K^n] key -> id or -1) is given. N < 2^31; K^n must fit 63 bits. */
+int pg_ngram_window_ids(int64_t nseq, const int64_t* offsets, const uint8_t* bytes, const int32_t* lut, int n,
+                        int64_t K, const int64_t* node_keys, int64_t N, const int32_t* table, int32_t* ids,
+                        void* stream);
+
+/* Mean of table rows per list: out[r] (r < P, stride ldo) = mean of E[ids[e]] (E [N, F] fp32, stride lde) over
+ * e in [rowptr[r], rowptr[r+1]) with 0 <= ids[e] < N (other entries are skipped; E is never read outside its N
+ * rows); counts[r] = the divisor; a list without a valid entry gives a row of +0.0 and count 0. rowptr may be the
+ * offsets given to pg_ngram_window_ids. Per feature column the sum is one sequential fp32 chain from +0.0 and the
+ * quotient is the correctly rounded fp32 one, so the result equals the reference's bit for bit:
+ *   distinct = 0  EmbeddingProcessor.pool_ngram_embeddings_for_protein (models_utils.py:197-207): every entry with
+ *                 its multiplicity, added in list order (np.mean(rows, axis=0));
+ *   distinct = 1  pool_ngram_embeddings_for_protein_fast (:209-262, the trainer's call): every id once, added in
+ *                 ascending id order (sums[prot_indices] += emb per n-gram id). Duplicates are removed in a
+ *                 per-list bitmap over the N nodes in LDS: N <= pg_pool_distinct_max_nodes() = 262144 (32 KiB per
+ *                 list in flight), else PG_ERR_UNSUPPORTED (sort the lists and use distinct = 0).
+ * `order` (optional, [P], a permutation of 0..P-1): the sequence in which lists are started (longest first keeps
+ * the tail of one sequential chain per list short); it does not change any result. Any F >= 1: 16-B pieces when
+ * F, lde, ldo are multiples of 4 and E, out are 16-B aligned, per element otherwise. flags: reserved (0). */
+int64_t pg_pool_distinct_max_nodes(void);
+int pg_pool_rows_f32(const float* E, int64_t lde, int64_t N, int64_t F, const int64_t* rowptr, const int32_t* ids,
+                     const int64_t* order, int64_t P, int distinct, float* out, int64_t ldo, int32_t* counts,
+                     uint32_t flags, void* stream);
+
 /* ---- training-step helpers (the trainer's L2 term over all parameters, trainer :96 / :136) ---------
  * A tensor list is a device array of descriptors; tensor t is split into pg_multi_chunks(numel_t) chunks of
  * 16K elements and chunk_ptr[t] = the first chunk of tensor t (exclusive prefix sum, chunk_ptr[ntens] =

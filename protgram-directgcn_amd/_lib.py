@@ -142,6 +142,10 @@ SIGNATURES = {
     "pg_directgcn_head_bf16": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32,
                                               c_vp, c_i64, c_vp, c_i64, c_vp]),
     "pg_ngram_keys": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_vp, c_vp]),
+    "pg_ngram_window_ids": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "pg_pool_distinct_max_nodes": (c_i64, []),
+    "pg_pool_rows_f32": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_i64,
+                                        c_vp, c_u32, c_vp]),
     "pg_multi_chunks": (c_i64, [c_i64]),
     "pg_multi_sqsum_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pg_multi_axpy_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
