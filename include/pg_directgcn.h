@@ -508,6 +508,32 @@ int pg_pool_rows_f32(const float* E, int64_t lde, int64_t N, int64_t F, const in
                      const int64_t* order, int64_t P, int distinct, float* out, int64_t ldo, int32_t* counts,
                      uint32_t flags, void* stream);
 
+/* ---- PCA reduction of the pooled table (protgram_directgcn_trainer.py:411-421, "Step 5";
+ * EmbeddingProcessor.apply_pca, models_utils.py:88-136) -----------------------------------------------------------
+ * The two streaming passes over X [P, F] fp32 (row stride ldx >= F, 1 <= F <= 512); the F x F eigenproblem between
+ * them is the caller's. `counts` (optional, int32 [P]): only rows with counts[r] > 0 take part, pg_pool_rows_f32's
+ * convention, so its output goes in uncompacted; NULL: every row. 16-B loads when F and ldx are multiples of 4 and
+ * X is 16-B aligned, per element otherwise.
+ *
+ * Moments, in float64 on the f64 matrix cores: out[a * F + b] = sum_r (x[r,a] - s[a]) (x[r,b] - s[b]) (the full
+ * symmetric F x F matrix), out[F*F + a] = sum_r (x[r,a] - s[a]), out[F*F + F] = the number of valid rows. `shift`
+ * (optional, float [F]): s, any vector near the data (e.g. one valid row), so that a large common offset does not
+ * cancel; NULL: s = 0. The rows are cut into chunks fixed by (P, F) alone, one partial per (chunk, tile) goes to
+ * `work` (pg_pca_moments_workspace(P, F) doubles; -1 for sizes that are not taken) and a second kernel adds the
+ * partials in a fixed order: no atomics, the same call gives the same bits. */
+int64_t pg_pca_moments_workspace(int64_t P, int64_t F);
+int pg_pca_moments_f64(const float* X, int64_t ldx, int64_t P, int64_t F, const int32_t* counts, const float* shift,
+                       double* out, double* work, int64_t work_doubles, void* stream);
+
+/* Projection: out[r, c] = sum_f (x[r,f] - center[f]) * W[c * F + f] for c < k (1 <= k <= F) and every valid row, a
+ * row of zeros for a skipped one. The subtraction is done in fp32 before the product, the product on the fp32
+ * matrix cores with fp32 accumulation; out_dtype 0: fp16, rounded once, to nearest even; 1: fp32. `out` has row
+ * stride ldo >= k elements; 16-B stores where out is 16-B aligned and ldo a multiple of 8 (fp16) or 4 (fp32).
+ * Standardisation, centring and the components' signs are folded into `center` and `W` by the caller: the kernel
+ * is a plain affine map. */
+int pg_pca_project(const float* X, int64_t ldx, int64_t P, int64_t F, const int32_t* counts, const float* center,
+                   const float* W, int64_t k, void* out, int64_t ldo, int out_dtype, void* stream);
+
 /* ---- training-step helpers (the trainer's L2 term over all parameters, trainer :96 / :136) ---------
  * A tensor list is a device array of descriptors; tensor t is split into pg_multi_chunks(numel_t) chunks of
  * 16K elements and chunk_ptr[t] = the first chunk of tensor t (exclusive prefix sum, chunk_ptr[ntens] =

@@ -146,6 +146,10 @@ SIGNATURES = {
     "pg_pool_distinct_max_nodes": (c_i64, []),
     "pg_pool_rows_f32": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_i64,
                                         c_vp, c_u32, c_vp]),
+    "pg_pca_moments_workspace": (c_i64, [c_i64, c_i64]),
+    "pg_pca_moments_f64": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "pg_pca_project": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.c_int,
+                                      c_vp]),
     "pg_multi_chunks": (c_i64, [c_i64]),
     "pg_multi_sqsum_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "pg_multi_axpy_f32": (ctypes.c_int, [ctypes.c_int, c_vp, c_vp, c_i64, c_f32, c_vp, c_vp]),
