@@ -16,6 +16,13 @@
  *    SOURCE node (ei[0]). Within a row, entries are sorted by ascending col: this is the order in
  *    which the reference's coalesced COO feeds scatter_add_, so accumulation order matches it.
  *  - Dense matrices are row-major fp32 with an explicit leading dimension (in elements).
+ *  - Memory contract: a call reads and writes the [rows, width] views of its operands only -- never the
+ *    ld - width pad elements of a row, a row outside the view, or an element past an exact-size flat buffer
+ *    (work, dW, dgate, gates, grads, loss, partial sums). Any ld >= width and any element-aligned base is a
+ *    legal argument: where a kernel needs more (ld a multiple of 4 or 8, a 16-B aligned base; stated per
+ *    entry point) the call either runs a slower kernel of the same contract or returns PG_ERR_UNSUPPORTED
+ *    before it launches anything, leaving every output as it was. tests/test_gpu_abi_layout.py holds the
+ *    outcome per entry point.
  */
 #ifndef PG_DIRECTGCN_H
 #define PG_DIRECTGCN_H
@@ -216,7 +223,11 @@ int pg_directgcn_pack_f32(const pg_layer_args_t* args, float* packed, void* stre
  * read); W_res != NULL selects the projected residual. packed == NULL: the kernel forms W_q + W_shared and the
  * bias sums from the W_* / b_* fields itself (the pack kernel's fp32 adds, so the result is identical), which
  * only the pipelined split-bf16 kernel does (F_in = F_out = 128, no W_res, no row map, 16-B aligned weights);
- * any other case returns PG_ERR_UNSUPPORTED without launching (callers then pack and call again). */
+ * any other case returns PG_ERR_UNSUPPORTED without launching (callers then pack and call again).
+ * Layouts (packed given): any. The contraction reads 16-B pieces where F_in and ldz (ld_res) are multiples of 4 and
+ * Z, packed (res_x) 16-B aligned, the epilogue where F_out, ldy, ld_const (ld_res of an identity residual) are
+ * multiples of 4 and Y, constant (res_x) 16-B aligned; either falls back to element accesses on its own, and the
+ * split-bf16 kernels need both. */
 int pg_directgcn_dense_f32(const pg_layer_args_t* args, const float* packed, uint32_t flags, void* stream);
 
 /* pg_directgcn_dense_f32 over the rows of a middle range in middle-major order (the rows
@@ -259,7 +270,9 @@ int pg_spmm3_gated_f32(int64_t n_rows, const int64_t* rowptr, const int32_t* row
  *   pg_spmm3t_ngram_f32: dX (+)= sum_k A_k G[:, kF:(k+1)F] for the symmetric n-gram matrices (A_k^T = A_k).
  *     F = 64, 128 or 256.
  *   pg_spmm3t_ngram_bf16: the transposed kernel on bf16 rows (the model's bf16 mode; replaces pg_spmm3t_bf16 on
- *     such graphs): fp32 sums, rounded once to bf16. F = 64, 128 or 256. */
+ *     such graphs): fp32 sums, rounded once to bf16. F = 64, 128 or 256.
+ *   All three: 16-B aligned rows of both matrices (16-B aligned bases, leading dimensions a multiple of 4 fp32 /
+ *     8 bf16 elements), PG_ERR_UNSUPPORTED otherwise (no launch). */
 int64_t pg_ngram_plan_floats(int K, int n, int64_t n_rows);
 int pg_ngram_plan_f32(int K, int n, int64_t n_rows, const int64_t* rowptr, const pg_edge3_t* edges, float* plan,
                       int64_t plan_floats, int* bad, void* stream);
@@ -359,7 +372,7 @@ int pg_spmm3t_ngram_mid_bf16(int K, int n, int64_t n_rows, const float* plan, co
  *   S: 2 n_own +    l*400 + c*20 + a  <- row c.a.M   sum_{k,b} Win_k[a,b,c] G_k[a.M.b]
  * (l = M - m0, n_own = n_mid * 400). The caller sums the parts of each global row (pg_rows_gather_sum). `splan` =
  * pg_ngram_scatter_plan of the same middles (78,000 floats per middle). F a multiple of 16; 16-B aligned G (ldg a
- * multiple of 8 bf16 / 4 fp32 elements) and T. Numerics: fp32 MFMA sums of the same w*g terms (bf16 G widened
+ * multiple of 8 bf16 / 4 fp32 elements) and T (ldt a multiple of 4), PG_ERR_UNSUPPORTED otherwise (no launch). Numerics: fp32 MFMA sums of the same w*g terms (bf16 G widened
  * exactly): within fp32 rounding of the CSR transposed kernel. */
 int pg_ngram_scatter_plan(int K, int n, const float* mplan, int64_t m0, int64_t n_mid, float* splan, void* stream);
 int pg_spmm3t_ngram_scatter_f32(const float* splan, int64_t n_mid, const float* G, int64_t ldg, int64_t F, float* T,
@@ -377,7 +390,8 @@ int pg_rows_scatter(const void* src, int64_t ld_src, const int64_t* idx, int64_t
                     int64_t ld_dst, void* stream);
 /* out[i] = sum of the rows listed for i, in list order, in fp32: entry idx[e] >= 0 is row idx[e] of A (fp32,
  * stride lda elements), idx[e] < 0 row -1 - idx[e] of B (bf16 if b_bf16 else fp32, stride ldb); entries of row i
- * are rowptr[i] .. rowptr[i+1]-1; out [n_out, F] fp32, or bf16 (one rounding) if out_bf16. F a multiple of 4. (The
+ * are rowptr[i] .. rowptr[i+1]-1; out [n_out, F] fp32, or bf16 (one rounding) if out_bf16. F a multiple of 4; lda,
+ * ldb, ldo multiples of 4 and 16-B aligned fp32 / 8-B aligned bf16 bases, else PG_ERR_UNSUPPORTED (no launch). (The
  * middle partition's backward: a row's scatter parts plus the rows received for it from the other ranks.) */
 int pg_rows_gather_sum(const float* A, int64_t lda, const void* B, int64_t ldb, int b_bf16, const int64_t* rowptr,
                        const int32_t* idx, int64_t n_out, int64_t F, void* out, int64_t ldo, int out_bf16,
@@ -392,13 +406,17 @@ int pg_rows_gather_sum(const float* A, int64_t lda, const void* B, int64_t ldb, 
  *   dgate [5, M]      per-row dL/d{c_in, c_out, c_directed, c_undirected, c_all} (row m uses gate row r(m))
  *   gates [M, 4]      the row gates s_in, s_out, s_und, 1 (scratch output)
  *   dW    [F_out*K + 4*F_out]  dL/dB in the packed layout: segment q of [F_out, K] is the gradient of
- *                     W_main_q + W_shared (W_res for q = 3); then [4, F_out] for the bias sums (b_res last)
+ *                     W_main_q + W_shared (W_res for q = 3); then [4, F_out] for the bias sums: rows 0..2 the
+ *                     gated sums sum_m s_q[m] dpre[m], row 3 the plain column sums of dpre (b_res's gradient
+ *                     with a projected residual; written without one too)
  * work: pg_directgcn_dense_bwd_workspace(args) floats. Deterministic (fixed-order reductions).
- * Returns PG_ERR_UNSUPPORTED unless F_in, F_out and every leading dimension are multiples of 4 and the
- * buffers 16-B aligned. Five launches on `stream`: transpose, dgrad (MFMA), gate grads, wgrad (MFMA,
- * split over rows), split reduction. Where F_out % 32 == 0 dgrad runs on the bf16 matrix cores in the exact
- * three-way split (six bf16 products per fp32 product, fp32 sums; the transpose also splits the packed weights),
- * unless flags has PG_FLAG_DGRAD_F32MFMA (the fp32-MFMA kernel). */
+ * Any shape and layout: where F_in, F_out and every leading dimension (ldz, ldy, lddy, ldp, lddz, and ld_res,
+ * lddres with a projected residual) are multiples of 4 and Z, Y, dY, dpre, dZ, gates, dW, work, packed (and
+ * res_x, dres) 16-B aligned, five launches on `stream`: transpose, dgrad (MFMA), gate grads, wgrad (MFMA, split
+ * over rows), split reduction; otherwise per-element kernels with the same outputs (sums in another order;
+ * F_out <= 8192, else PG_ERR_ARG). On the MFMA path, where F_out % 32 == 0 dgrad runs on the bf16 matrix cores in
+ * the exact three-way split (six bf16 products per fp32 product, fp32 sums; the transpose also splits the packed
+ * weights), unless flags has PG_FLAG_DGRAD_F32MFMA (the fp32-MFMA kernel). */
 typedef struct pg_layer_grad_args {
     const float* dY; int64_t lddy;
     float* dpre; int64_t ldp;
@@ -452,15 +470,16 @@ int pg_spmm3t_bf16(int64_t n_rows, const int64_t* rowptr, const int32_t* row_ord
 /* pg_directgcn_dense_f32 on bf16 MFMA (v_mfma_f32_32x32x16_bf16). In `args`, Z, res_x and Y point to bf16
  * data (their float* types are reinterpreted); gates, constant and the bias sums (read from the fp32
  * `packed`) stay fp32. `packed_bf16` = pg_f32_to_bf16 of the first F_out*K floats of `packed`. Needs
- * F_in % 8 == 0, F_out % 4 == 0, ldz and ld_res multiples of 8, 16-B aligned Z / res_x / packed_bf16 /
- * constant, 8-B aligned Y (else PG_ERR_UNSUPPORTED). */
+ * F_in % 8 == 0, F_out % 4 == 0, ldz and ld_res multiples of 8, ldy and ld_const multiples of 4, 16-B aligned
+ * Z / res_x / packed_bf16 / constant, 8-B aligned Y (else PG_ERR_UNSUPPORTED). */
 int pg_directgcn_dense_bf16(const pg_layer_args_t* args, const float* packed, const uint16_t* packed_bf16,
                             uint32_t flags, void* stream);
 
 /* pg_directgcn_dense_bwd_f32 in bf16 mode (bf16 MFMA products, fp32 sums): in `args` Z, res_x and Y are
  * bf16, in `grads` dY, dpre, dZ and dres are bf16; dgate, gates, dW and work stay fp32. Same workspace
  * (pg_directgcn_dense_bwd_workspace) and output layout as the fp32 entry point. Needs F_in, F_out and
- * every leading dimension a multiple of 8 and 16-B aligned buffers (else PG_ERR_UNSUPPORTED). */
+ * every leading dimension a multiple of 8 and 16-B aligned buffers, dpre_f32 (when given) 16-B aligned with
+ * ldp_f32 a multiple of 4 (else PG_ERR_UNSUPPORTED, before anything is launched). */
 int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* args, const float* packed, const uint16_t* packed_bf16,
                                 const pg_layer_grad_args_t* grads, uint32_t flags, void* stream);
 
@@ -610,7 +629,8 @@ int pg_multi_sum_f32(int64_t n, const float* x, float* out, void* stream);
  * with s = *grad_scale (or 1): dh [M, F] and grads = [dW1 (H x F) | db1 (H) | dW2 (C x H) | db2 (C)] of s * loss;
  * loss[0] = the unscaled loss. drop_p > 0: keep element (m, j) of a by a counter-based draw from seed[0] (device
  * int64), scaled by 1 / (1 - drop_p). W1 [H, F], W2 [C, H] row-major (nn.Linear weights); y int64 [M].
- * F = 128, H = 64, C <= 32 only (PG_ERR_UNSUPPORTED otherwise). work: pg_head_train_workspace floats. */
+ * F = 128, H = 64, C <= 32 only, h 16-B aligned with ldh a multiple of 4 (PG_ERR_UNSUPPORTED otherwise, no launch;
+ * dh takes any lddh >= F). work: pg_head_train_workspace floats. */
 int64_t pg_head_train_workspace(int64_t M, int64_t F, int64_t H, int64_t C);
 int pg_head_train_f32(int64_t M, int64_t F, int64_t H, int64_t C, const float* h, int64_t ldh, const float* W1,
                       const float* b1, const float* W2, const float* b2, const int64_t* y, float loss_weight,
@@ -620,7 +640,8 @@ int pg_head_train_f32(int64_t M, int64_t F, int64_t H, int64_t C, const float* h
 /* The same step in the model's bf16 mode at F = 256, H = 128, C <= 32 (config 5's head): h and dh are bf16 rows (dh
  * rounded once); the products run on the bf16 matrix cores with two-term bf16 splits of the fp32 operands (each
  * product within ~2^-15 relative of fp32), fp32 sums; loss and grads fp32 as pg_head_train_f32. work:
- * pg_head_train_bf16_workspace floats; other shapes: PG_ERR_UNSUPPORTED (-1 from the workspace query). */
+ * pg_head_train_bf16_workspace floats; other shapes: PG_ERR_UNSUPPORTED (-1 from the workspace query), as are h, dh or
+ * W1 that are not 16-B aligned and ldh, lddh that are not multiples of 8 (no launch). */
 int64_t pg_head_train_bf16_workspace(int64_t M, int64_t F, int64_t H, int64_t C);
 int pg_head_train_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uint16_t* h, int64_t ldh, const float* W1,
                        const float* b1, const float* W2, const float* b2, const int64_t* y, float loss_weight,
@@ -650,7 +671,8 @@ int pg_dense_grads_layout_f32(int64_t F_out, int64_t F_in, int32_t S, const floa
 /* Fused prediction head (protgram_directgcn.py:218-222, eval mode): per row m of h [M, F]
  *   logp[m] = log_softmax(W2 relu(W1 h[m] + b1) + b2)      W1 [H, F], W2 [C, H] (nn.Linear layout)
  *   emb[m]  = h[m] / (||h[m]||_2 + eps)                      (models_utils.py:139-147)
- * One read of h; both products on fp32 MFMA for F <= 256, H <= 128, C <= 64, else a VALU kernel. */
+ * One read of h; both products on fp32 MFMA for F <= 256, H <= 128, C <= 64 with F, H, ldh, lde multiples of 4 and
+ * 16-B aligned h, emb, W1, W2; any other shape or layout: a VALU kernel (logp takes any ldp >= C either way). */
 int pg_directgcn_head_f32(int64_t M, int64_t F, int64_t H, int64_t C, const float* h, int64_t ldh,
                           const float* W1, const float* b1, const float* W2, const float* b2, float eps,
                           float* logp, int64_t ldp, float* emb, int64_t lde, void* stream);

@@ -2456,8 +2456,9 @@ __global__ __launch_bounds__(256) void wgrad_generic_kernel(WgradGenP w) {
     } else {
         const int64_t t = idx - (int64_t)w.F_out * w.K;
         const int q = (int)(t / w.F_out), o = (int)(t % w.F_out);
-        if (q < 3 || w.proj)
-            for (int64_t m = m0; m < m1; ++m) acc += (q < 3 ? w.gates[m * 4 + q] : 1.f) * w.dpre[m * w.ldp + o];
+        // row 3 = the column sums of dpre with or without a projected residual, as the MFMA kernels give it (their
+        // fourth gate column is 1): the same dW whichever kernels a layout selects
+        for (int64_t m = m0; m < m1; ++m) acc += (q < 3 ? w.gates[m * 4 + q] : 1.f) * w.dpre[m * w.ldp + o];
         out = (int64_t)w.F_out * w.K + (int64_t)q * w.F_out + o;
     }
     w.part[(int64_t)blockIdx.y * w.part_stride + out] = acc;
@@ -2818,12 +2819,13 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
                                (reinterpret_cast<uintptr_t>(drb) & 7) == 0)) &&
                     pg::aligned16(Zb) && pg::aligned16(dYb) && pg::aligned16(dpb) && pg::aligned16(g->gates) &&
                     pg::aligned16(g->dW) && pg::aligned16(g->work) && pg::aligned16(packed) &&
-                    pg::aligned16(packed_bf16) && (!a->act || pg::aligned16(Yb));
+                    pg::aligned16(packed_bf16) && (!a->act || pg::aligned16(Yb)) &&
+                    (!g->dpre_f32 || (g->ldp_f32 % 4 == 0 && pg::aligned16(g->dpre_f32)));
     if (!ok)
         return pg::set_error(PG_ERR_UNSUPPORTED, "pg_directgcn_dense_bwd_bf16: needs F_in, F_out and leading dims "
                                                  "multiples of 8 and aligned buffers");
     PG_REQUIRE(a->ldz >= 3 * a->F_in && (!dZb || g->lddz >= 3 * a->F_in) && g->lddy >= a->F_out &&
-                   g->ldp >= a->F_out,
+                   g->ldp >= a->F_out && (!g->dpre_f32 || g->ldp_f32 >= a->F_out),
                "leading dimensions too small");
     hipStream_t s = (hipStream_t)stream;
     const int K = pl.K;
@@ -2869,8 +2871,6 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
         p.gates = g->gates;
         p.dsp = dsp;
         p.remap = (flags & PG_FLAG_NO_XCD_REMAP) ? 0 : 1;
-        PG_REQUIRE(!g->dpre_f32 || (g->ldp_f32 >= F_out && g->ldp_f32 % 4 == 0 && pg::aligned16(g->dpre_f32)),
-                   "dpre_f32 needs ldp_f32 >= F_out, a multiple of 4, and a 16-B aligned buffer");
         p.dpre32 = g->dpre_f32;
         p.ldp32 = g->ldp_f32;
         // resident-A kernel: 64-row workgroups, two per CU; below 256 rows per CU (a P = 8 rank's 20,000 rows: 313

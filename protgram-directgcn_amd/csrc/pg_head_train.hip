@@ -763,9 +763,11 @@ int pg_head_train_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uint16_
     if (F != h5::F || H != h5::H || C < 1 || C > TC)
         return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_bf16: F = 256, H = 128, C <= 32 only");
     PG_REQUIRE(M >= 0 && h && W1 && b1 && W2 && b2 && y && dh && grads && loss && work, "null argument");
-    PG_REQUIRE(ldh >= F && lddh >= F && ldh % 8 == 0 && lddh % 8 == 0 && pg::aligned16(h) && pg::aligned16(dh),
-               "h, dh: 16-B aligned bf16 rows of F elements");
-    PG_REQUIRE(pg::aligned16(W1), "W1: 16-B aligned");
+    PG_REQUIRE(ldh >= F && lddh >= F, "h, dh: rows of F elements");
+    // a layout the 16-B row pieces do not take is a legal argument: declined before any launch, as a shape is
+    if (ldh % 8 || lddh % 8 || !pg::aligned16(h) || !pg::aligned16(dh) || !pg::aligned16(W1))
+        return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_bf16: needs ldh, lddh multiples of 8 and 16-B aligned "
+                                                 "h, dh, W1");
     PG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "drop_p in [0, 1)");
     PG_REQUIRE(drop_p == 0.f || seed, "dropout needs a seed");
     PG_REQUIRE(work_floats >= pg_head_train_bf16_workspace(M, F, H, C), "workspace too small");
@@ -812,7 +814,9 @@ int pg_head_train_f32(int64_t M, int64_t F, int64_t H, int64_t C, const float* h
     if (!shape_ok(F, H, C))
         return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_f32: F = 128, H = 64, C <= 32 only");
     PG_REQUIRE(M >= 0 && h && W1 && b1 && W2 && b2 && y && dh && grads && loss && work, "null argument");
-    PG_REQUIRE(ldh >= F && lddh >= F && ldh % 4 == 0 && pg::aligned16(h), "h: aligned rows of F floats");
+    PG_REQUIRE(ldh >= F && lddh >= F, "h, dh: rows of F floats");
+    if (ldh % 4 || !pg::aligned16(h))  // a legal layout the 16-B loads of h do not take: declined before any launch
+        return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_f32: needs ldh a multiple of 4 and a 16-B aligned h");
     PG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "drop_p in [0, 1)");
     PG_REQUIRE(drop_p == 0.f || seed, "dropout needs a seed");
     PG_REQUIRE(work_floats >= pg_head_train_workspace(M, F, H, C), "workspace too small");

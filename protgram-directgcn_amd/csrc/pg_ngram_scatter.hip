@@ -303,8 +303,9 @@ int scatter_launch(const float* splan, int64_t n_mid, const void* G, int64_t ldg
     PG_REQUIRE(splan && G && T, "%s: null pointer", name);
     PG_REQUIRE(F % 16 == 0, "%s: F = %lld must be a multiple of 16", name, (long long)F);
     PG_REQUIRE(ldg >= 3 * F && ldt >= F, "%s: row strides smaller than the rows", name);
-    PG_REQUIRE(ldg % (BF ? 8 : 4) == 0 && pg::aligned16(G) && pg::aligned16(T) && ldt % 4 == 0,
-               "%s: G rows must be 16-B aligned pieces (ldg %% %d == 0, 16-B base) and T 16-B aligned", name, BF ? 8 : 4);
+    if (ldg % (BF ? 8 : 4) || !pg::aligned16(G) || !pg::aligned16(T) || ldt % 4)  // a legal layout: declined, no launch
+        return pg::set_error(PG_ERR_UNSUPPORTED, "%s: G rows must be 16-B aligned pieces (ldg %% %d == 0, 16-B base) "
+                                                 "and T rows 16-B aligned (ldt %% 4 == 0)", name, BF ? 8 : 4);
     PG_REQUIRE((int64_t)SR * ldg < (int64_t)1 << 31, "%s: a middle's G rows exceed 2^31 elements", name);
     PG_REQUIRE((int64_t)SR * ldt * 4 < (int64_t)1 << 30, "%s: a middle's T rows exceed 2^30 bytes", name);
     SP p;

@@ -120,11 +120,13 @@ int pg_rows_gather_sum(const float* A, int64_t lda, const void* B, int64_t ldb, 
     if (n_out == 0 || F == 0) return PG_OK;
     PG_REQUIRE(rowptr && idx && out, "%s: null pointer", name);
     PG_REQUIRE(F % 4 == 0, "%s: F = %lld must be a multiple of 4", name, (long long)F);
-    PG_REQUIRE(lda >= F && ldb >= F && ldo >= F && lda % 4 == 0 && ldb % 4 == 0 && ldo % 4 == 0,
-               "%s: row strides must be >= F and multiples of 4", name);
-    PG_REQUIRE((!A || pg::aligned16(A)) && (!B || (reinterpret_cast<uintptr_t>(B) & (b_bf16 ? 7u : 15u)) == 0) &&
-                   (reinterpret_cast<uintptr_t>(out) & (out_bf16 ? 7u : 15u)) == 0,
-               "%s: misaligned base pointer", name);
+    PG_REQUIRE(lda >= F && ldb >= F && ldo >= F, "%s: row strides must be >= F", name);
+    // strides and bases the 4-element pieces do not take are legal arguments: declined before the launch
+    if (lda % 4 || ldb % 4 || ldo % 4 || (A && !pg::aligned16(A)) ||
+        (B && (reinterpret_cast<uintptr_t>(B) & (b_bf16 ? 7u : 15u)) != 0) ||
+        (reinterpret_cast<uintptr_t>(out) & (out_bf16 ? 7u : 15u)) != 0)
+        return pg::set_error(PG_ERR_UNSUPPORTED, "%s: needs row strides that are multiples of 4 and 16-B aligned "
+                                                 "(bf16: 8-B) bases", name);
     const int q4 = (int)(F / 4);
     const int64_t blocks = (n_out * q4 + 255) / 256;
     const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
