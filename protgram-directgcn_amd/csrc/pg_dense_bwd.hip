@@ -35,7 +35,8 @@ namespace {
 // One row's gate partials over the C4 4-column groups of an n-tile (the per-column dots the epilogue left in T at
 // stride 4), added into ds[segment] in column order -- the order of the original serial loop, so the same bits --
 // with the LDS reads issued in groups of 8: C4 / 8 round trips per row instead of C4 dependent ones (the serial loop with its
-// early exit and division cost the resident bf16 dgrad ~70 us of its ~300 at config 5, tools/r06_dgrad_exp.sh).
+// early exit and division cost the resident bf16 dgrad ~70 us of its ~300 at config 5; measured with a phase-skipping
+// diagnostics build that has since been removed, profiles/r06_dgrad_exp.txt).
 template <int C4>
 __device__ __forceinline__ void row_gate_partials(const float* Trow, int n0, int N, int F_in, float (&ds)[3]) {
     constexpr int G = C4 < 8 ? C4 : 8;
@@ -77,34 +78,248 @@ __device__ __forceinline__ void gate_values(const Gates& g, int64_t m, float& ci
     ca = g.C_all[r];
 }
 
+// E: the activations' element, float (fp32 mode) or uint16_t (bf16 bits)
+template <typename E>
 struct DgradP {
     int64_t M;
     int F_in, F_out, N;  // N = forward K (3 or 4 segments of F_in)
-    const float* dY;
+    const E* dY;
     int64_t lddy;
-    const float* Y;
+    const E* Y;
     int64_t ldy;
     int act;
     float slope;
     float drop_s;       // fused layer dropout's scale (pg::act_grad), 0: none
-    const float* BT;    // [N, F_out]
+    const E* BT;        // [N, F_out]
     const float* bsum;  // [4, F_out]
-    const float* Z;
+    const E* Z;
     int64_t ldz;
     Gates g;
-    float* dpre;
+    E* dpre;
     int64_t ldp;
-    float* dZ;
+    E* dZ;
     int64_t lddz;
-    float* dres;
+    E* dres;
     int64_t lddres;
     float* gates;  // [M, 4]
     float* dsp;    // [ntn * 3, M]
     int remap;
+    float* dpre32;  // bf16 mode: optional fp32 copy of dpre (the rounded values), or null; fp32 mode: null
+    int64_t ldp32;
 };
 
+// ------------------------------------------------------------------------------------------------
+// Stages shared by the MFMA dgrad kernels (each kernel's own comment says which it uses and why it differs)
+// ------------------------------------------------------------------------------------------------
+
+// dpre = dY * act'(Y) (pg::act_grad) on a float4, and on 8 unpacked bf16 values
+__device__ __forceinline__ float4 act_grad4(float4 d, float4 y, float slope, float drop_s) {
+    d.x = pg::act_grad(d.x, y.x, slope, drop_s);
+    d.y = pg::act_grad(d.y, y.y, slope, drop_s);
+    d.z = pg::act_grad(d.z, y.z, slope, drop_s);
+    d.w = pg::act_grad(d.w, y.w, slope, drop_s);
+    return d;
+}
+__device__ __forceinline__ void act_grad8(float (&d)[8], const float (&y)[8], float slope, float drop_s) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) d[e] = pg::act_grad(d[e], y[e], slope, drop_s);
+}
+
+// Row-gate prologue: thread tid < BM computes s_q of row m0 + tid into Sg (rows past M: 0, 0, 0, 1) and, where
+// `store` (the lead n-tile; the resident kernel owns all n-tiles of its rows: always), into gates for the weight
+// gradient. SPAN: the row's Wdiag_q into Wd as well (dgrad_span_kernel).
+template <int BM, bool SPAN = false>
+__device__ __forceinline__ void row_gate_prologue(const Gates& g, int64_t m0, int64_t M, int tid, bool store,
+                                                  float* gates, float* Sg, const float* wdiag = nullptr,
+                                                  float* Wd = nullptr) {
+    if (tid < BM) {
+        const int64_t m = m0 + tid;
+        float4 sv = make_float4(0.f, 0.f, 0.f, 1.f);
+        float w0 = 0.f, w1 = 0.f, w2 = 0.f;
+        if (m < M) {
+            float ci, co, cd, cu, ca;
+            gate_values(g, m, ci, co, cd, cu, ca);
+            const float cad = ca * cd;
+            sv.x = cad * ci;
+            sv.y = cad * co;
+            sv.z = ca * cu;
+            if (store) st4(gates + m * 4, sv);
+            if constexpr (SPAN) {
+                w0 = wdiag[m * 3 + 0];
+                w1 = wdiag[m * 3 + 1];
+                w2 = wdiag[m * 3 + 2];
+            }
+        }
+        st4(&Sg[tid * 4], sv);
+        if constexpr (SPAN) {
+            Wd[tid * 3 + 0] = w0;
+            Wd[tid * 3 + 1] = w1;
+            Wd[tid * 3 + 2] = w2;
+        }
+    }
+}
+
+// bias dots <dpre[m], bsum_q>: 8 consecutive lanes hold one row's K slices; piece q of thread tid is row
+// (tid + NT q) >> 3
+template <int NQ, int NT>
+__device__ __forceinline__ void bias_dot_reduce(float (&bd)[NQ][3], int tid, float* Bd) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+#pragma unroll
+        for (int s = 0; s < 3; ++s) {
+            float v = bd[q][s];
+            v += __shfl_xor(v, 1);
+            v += __shfl_xor(v, 2);
+            v += __shfl_xor(v, 4);
+            bd[q][s] = v;
+        }
+        const int idx = tid + NT * q;
+        if ((idx & 7) == 0) {
+            Bd[(idx >> 3) * 3 + 0] = bd[q][0];
+            Bd[(idx >> 3) * 3 + 1] = bd[q][1];
+            Bd[(idx >> 3) * 3 + 2] = bd[q][2];
+        }
+    }
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void acc_zero(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// Park a wave's 32x32 accumulator tiles in the LDS tile T (row stride tld): tile (i, j) at rows row0 + 32 i,
+// columns col0 + cstride j; register r of lane (li, lh) is row (r & 3) + 8 (r >> 2) + 4 lh, column li of its tile.
+template <int TM, int TN>
+__device__ __forceinline__ void acc_park(const f32x16 (&acc)[TM][TN], float* T, int tld, int row0, int col0,
+                                         int cstride, int li, int lh) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int rl = row0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                T[rl * tld + col0 + j * cstride + li] = acc[i][j][r];
+            }
+}
+
+// fp32 A-operand stage, k-tiles of 32: piece q of thread tid is row (tid + NT q) >> 3, columns k0 + 4 ((tid + NT q) & 7).
+// KCHECK: F_out may end inside a k-tile (the span kernel's host check excludes it: no clamps or selects there).
+template <int A_F4, int NT, bool KCHECK>
+__device__ __forceinline__ void a_fetch_f32(const DgradP<float>& p, int64_t m0, int tid, int k0, float4 (&ra)[A_F4],
+                                            float4 (&ry)[A_F4]) {
+#pragma unroll
+    for (int q = 0; q < A_F4; ++q) {
+        const int idx = tid + NT * q;
+        const int64_t m = min(m0 + (idx >> 3), p.M - 1);
+        const int k = k0 + 4 * (idx & 7);
+        const int kc = !KCHECK || k < p.F_out ? k : 0;
+        ra[q] = ld4(p.dY + m * p.lddy + kc);
+        if (p.act) ry[q] = ld4(p.Y + m * p.ldy + kc);
+    }
+}
+// dpre of the fetched pieces; the lead n-tile stores it and adds its bias dots; write(idx, d) puts it into LDS
+// (dgrad_kernel, dgrad_x3_kernel; dgrad_span_kernel keeps its own copy, without the k checks)
+template <int A_F4, int NT, class Write>
+__device__ __forceinline__ void a_stage_f32(const DgradP<float>& p, bool lead, int64_t m0, int tid, int k0,
+                                            const float4 (&ra)[A_F4], const float4 (&ry)[A_F4], float (&bd)[A_F4][3],
+                                            Write write) {
+#pragma unroll
+    for (int q = 0; q < A_F4; ++q) {
+        const int idx = tid + NT * q;
+        const int k = k0 + 4 * (idx & 7);
+        const int64_t m = m0 + (idx >> 3);
+        float4 d = ra[q];
+        if (p.act) d = act_grad4(d, ry[q], p.slope, p.drop_s);
+        if (k >= p.F_out) d = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lead && k < p.F_out && m < p.M) {
+            st4(p.dpre + m * p.ldp + k, d);
+#pragma unroll
+            for (int s = 0; s < 3; ++s) bd[q][s] += dot4(d, ld4(p.bsum + s * p.F_out + k));
+        }
+        write(idx, d);
+    }
+}
+
+// Per-row gate partials of one n-tile into dsp: thread tid < BM adds its row's products (left in T at stride 4 by the
+// tile epilogue) to the lead tile's bias dots. SERIAL: the original column loop instead of row_gate_partials (the same
+// order, the same bits).
+template <int BM, int C4, bool SERIAL, typename E>
+__device__ __forceinline__ void row_dsp_store(const DgradP<E>& p, const float* T, int tld, const float* Bd, bool lead,
+                                              int tid, int64_t m0, int n0, int nt) {
+    if (tid < BM && m0 + tid < p.M) {
+        const int64_t m = m0 + tid;
+        float ds[3] = {0.f, 0.f, 0.f};
+        if (lead) {
+            ds[0] = Bd[tid * 3 + 0];
+            ds[1] = Bd[tid * 3 + 1];
+            ds[2] = Bd[tid * 3 + 2];
+        }
+        if constexpr (SERIAL) {
+            for (int c = 0; c < C4; ++c) {
+                const int jj = n0 + 4 * c;
+                if (jj >= p.N) break;
+                const int q = jj / p.F_in;
+                if (q < 3) ds[q] += T[tid * tld + 4 * c];
+            }
+        } else {
+            row_gate_partials<C4>(&T[tid * tld], n0, p.N, p.F_in, ds);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) p.dsp[((int64_t)nt * 3 + q) * p.M + m] = ds[q];
+    }
+}
+
+// fp32 tile epilogue (dgrad_kernel, dgrad_x3_kernel): the tile G is parked in T; streams Z in and dZ / dres out with
+// float4 accesses, leaves <G_q, Z_q> per (row, 4 columns) in T, then reduces them per row in fixed order into dsp.
+template <int BM, int BN, int NT, bool SERIAL>
+__device__ __forceinline__ void tile_epilogue_f32(const DgradP<float>& p, float* T, const float* Sg, const float* Bd,
+                                                  bool lead, int tid, int64_t m0, int n0, int nt) {
+    constexpr int TLD = BN + 4;
+    constexpr int C4 = BN / 4;
+    constexpr int ITER = BM * C4 / NT;
+    constexpr int BATCH = ITER < 4 ? ITER : 4;
+    const int c4 = tid % C4;
+    const int j = n0 + 4 * c4;
+    const int seg = j < p.N ? j / p.F_in : 4;  // F_in % 4 == 0: a float4 never straddles segments
+    for (int it0 = 0; it0 < ITER; it0 += BATCH) {
+        float4 zv[BATCH];
+        int rl[BATCH];
+        int64_t mm[BATCH];
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            rl[u] = (tid + NT * (it0 + u)) / C4;
+            mm[u] = m0 + rl[u];
+            zv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (mm[u] < p.M && seg < 3) zv[u] = ld4(p.Z + mm[u] * p.ldz + j);
+        }
+#pragma unroll
+        for (int u = 0; u < BATCH; ++u) {
+            float part = 0.f;
+            if (mm[u] < p.M && seg < 4) {
+                const float4 gv = ld4(&T[rl[u] * TLD + 4 * c4]);
+                if (seg < 3) {
+                    const float s = Sg[rl[u] * 4 + seg];
+                    if (p.dZ) st4(p.dZ + mm[u] * p.lddz + j, make_float4(s * gv.x, s * gv.y, s * gv.z, s * gv.w));
+                    part = dot4(gv, zv[u]);
+                } else {
+                    st4(p.dres + mm[u] * p.lddres + (j - 3 * p.F_in), gv);
+                }
+            }
+            T[rl[u] * TLD + 4 * c4] = part;  // own slot, already consumed
+        }
+    }
+    __syncthreads();
+    row_dsp_store<BM, C4, SERIAL>(p, T, TLD, Bd, lead, tid, m0, n0, nt);
+}
+
 template <int BM, int BN, int NW>
-__global__ __launch_bounds__(64 * NW) void dgrad_kernel(DgradP p) {
+__global__ __launch_bounds__(64 * NW) void dgrad_kernel(DgradP<float> p) {
     constexpr int NT = 64 * NW;
     constexpr int WN = 2;
     constexpr int WM = NW / WN;
@@ -136,44 +351,17 @@ __global__ __launch_bounds__(64 * NW) void dgrad_kernel(DgradP p) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    if (tid < BM) {
-        const int64_t m = m0 + tid;
-        float4 s = make_float4(0.f, 0.f, 0.f, 1.f);
-        if (m < p.M) {
-            float ci, co, cd, cu, ca;
-            gate_values(p.g, m, ci, co, cd, cu, ca);
-            const float cad = ca * cd;
-            s.x = cad * ci;
-            s.y = cad * co;
-            s.z = ca * cu;
-            if (lead) st4(p.gates + m * 4, s);
-        }
-        st4(&Sg[tid * 4], s);
-    }
+    row_gate_prologue<BM>(p.g, m0, p.M, tid, lead, p.gates, Sg);
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     float4 ra[A_F4], ry[A_F4], rb[B_F4];
     float bd[A_F4][3];
 #pragma unroll
     for (int q = 0; q < A_F4; ++q) bd[q][0] = bd[q][1] = bd[q][2] = 0.f;
-    const int64_t mlast = p.M - 1;
     auto fetch = [&](int k0) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const int idx = tid + NT * q;
-            const int64_t m = min(m0 + (idx >> 3), mlast);
-            const int k = k0 + 4 * (idx & 7);
-            const int kc = k < p.F_out ? k : 0;
-            ra[q] = ld4(p.dY + m * p.lddy + kc);
-            if (p.act) ry[q] = ld4(p.Y + m * p.ldy + kc);
-        }
+        a_fetch_f32<A_F4, NT, true>(p, m0, tid, k0, ra, ry);
 #pragma unroll
         for (int q = 0; q < B_F4; ++q) {
             const int idx = tid + NT * q;
@@ -183,27 +371,9 @@ __global__ __launch_bounds__(64 * NW) void dgrad_kernel(DgradP p) {
         }
     };
     auto stash = [&](int buf, int k0) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const int idx = tid + NT * q;
-            const int k = k0 + 4 * (idx & 7);
-            const int64_t m = m0 + (idx >> 3);
-            float4 d = ra[q];
-            if (p.act) {
-                const float4 y = ry[q];
-                d.x = pg::act_grad(d.x, y.x, p.slope, p.drop_s);
-                d.y = pg::act_grad(d.y, y.y, p.slope, p.drop_s);
-                d.z = pg::act_grad(d.z, y.z, p.slope, p.drop_s);
-                d.w = pg::act_grad(d.w, y.w, p.slope, p.drop_s);
-            }
-            if (k >= p.F_out) d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (lead && k < p.F_out && m < p.M) {
-                st4(p.dpre + m * p.ldp + k, d);
-#pragma unroll
-                for (int s = 0; s < 3; ++s) bd[q][s] += dot4(d, ld4(p.bsum + s * p.F_out + k));
-            }
+        a_stage_f32<A_F4, NT>(p, lead, m0, tid, k0, ra, ry, bd, [&](int idx, float4 d) {
             st4(&As[buf][(idx >> 3) * LDSW + 4 * (idx & 7)], d);
-        }
+        });
 #pragma unroll
         for (int q = 0; q < B_F4; ++q) {
             const int idx = tid + NT * q;
@@ -242,28 +412,9 @@ __global__ __launch_bounds__(64 * NW) void dgrad_kernel(DgradP p) {
         __syncthreads();
     }
 
-    // bias dots <dpre[m], bsum_q>: 8 consecutive lanes hold one row's K slices
-    if (lead) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-#pragma unroll
-            for (int s = 0; s < 3; ++s) {
-                float v = bd[q][s];
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                bd[q][s] = v;
-            }
-            const int idx = tid + NT * q;
-            if ((idx & 7) == 0) {
-                Bd[(idx >> 3) * 3 + 0] = bd[q][0];
-                Bd[(idx >> 3) * 3 + 1] = bd[q][1];
-                Bd[(idx >> 3) * 3 + 2] = bd[q][2];
-            }
-        }
-    }
-
+    if (lead) bias_dot_reduce<A_F4, NT>(bd, tid, Bd);
     float* T = smem;
+    // acc_park, kept as this kernel's own copy: through the shared template it took 119 VGPRs instead of 118
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -274,58 +425,8 @@ __global__ __launch_bounds__(64 * NW) void dgrad_kernel(DgradP p) {
                 T[rl * TLD + wn * TN * 32 + j * 32 + li] = acc[i][j][r];
             }
     __syncthreads();
-
-    constexpr int C4 = BN / 4;
-    constexpr int ITER = BM * C4 / NT;
-    constexpr int BATCH = ITER < 4 ? ITER : 4;
-    const int c4 = tid % C4;
-    const int j = n0 + 4 * c4;
-    const int seg = j < p.N ? j / p.F_in : 4;  // F_in % 4 == 0: a float4 never straddles segments
-    for (int it0 = 0; it0 < ITER; it0 += BATCH) {
-        float4 zv[BATCH];
-        int rl[BATCH];
-        int64_t mm[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            rl[u] = (tid + NT * (it0 + u)) / C4;
-            mm[u] = m0 + rl[u];
-            zv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (mm[u] < p.M && seg < 3) zv[u] = ld4(p.Z + mm[u] * p.ldz + j);
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            float part = 0.f;
-            if (mm[u] < p.M && seg < 4) {
-                const float4 gv = ld4(&T[rl[u] * TLD + 4 * c4]);
-                if (seg < 3) {
-                    const float s = Sg[rl[u] * 4 + seg];
-                    if (p.dZ) st4(p.dZ + mm[u] * p.lddz + j, make_float4(s * gv.x, s * gv.y, s * gv.z, s * gv.w));
-                    part = dot4(gv, zv[u]);
-                } else {
-                    st4(p.dres + mm[u] * p.lddres + (j - 3 * p.F_in), gv);
-                }
-            }
-            T[rl[u] * TLD + 4 * c4] = part;  // own slot, already consumed
-        }
-    }
-    __syncthreads();
-    if (tid < BM && m0 + tid < p.M) {
-        const int64_t m = m0 + tid;
-        float ds[3] = {0.f, 0.f, 0.f};
-        if (lead) {
-            ds[0] = Bd[tid * 3 + 0];
-            ds[1] = Bd[tid * 3 + 1];
-            ds[2] = Bd[tid * 3 + 2];
-        }
-        for (int c = 0; c < C4; ++c) {
-            const int jj = n0 + 4 * c;
-            if (jj >= p.N) break;
-            const int q = jj / p.F_in;
-            if (q < 3) ds[q] += T[tid * TLD + 4 * c];
-        }  // (row_gate_partials spilled 16 B per lane here)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) p.dsp[((int64_t)nt * 3 + q) * p.M + m] = ds[q];
-    }
+    // the serial gate-partials loop: row_gate_partials spilled 16 B per lane here
+    tile_epilogue_f32<BM, BN, NT, true>(p, T, Sg, Bd, lead, tid, m0, n0, nt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -361,9 +462,17 @@ __device__ __forceinline__ void split4(float4 v, uint2& s0, uint2& s1, uint2& s2
     w1 = pgx3::bf2(c, d, fc, fd);
     s2 = make_uint2(w0, w1);
 }
+// the LDS write of the x3 kernel's A stage: the three split images of a float4 at image offset o
+__device__ __forceinline__ void split4_store(float4 d, int o, uint16_t* i0, uint16_t* i1, uint16_t* i2) {
+    uint2 s0, s1, s2;
+    split4(d, s0, s1, s2);
+    *reinterpret_cast<uint2*>(i0 + o) = s0;
+    *reinterpret_cast<uint2*>(i1 + o) = s1;
+    *reinterpret_cast<uint2*>(i2 + o) = s2;
+}
 
 template <int BM, int BN, int NW>
-__global__ __launch_bounds__(64 * NW, 3) void dgrad_x3_kernel(DgradP p, const uint16_t* BT3) {
+__global__ __launch_bounds__(64 * NW, 3) void dgrad_x3_kernel(DgradP<float> p, const uint16_t* BT3) {
     constexpr int NT = 64 * NW;
     constexpr int WN = 2;
     constexpr int WM = NW / WN;
@@ -395,46 +504,19 @@ __global__ __launch_bounds__(64 * NW, 3) void dgrad_x3_kernel(DgradP p, const ui
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    if (tid < BM) {
-        const int64_t m = m0 + tid;
-        float4 sv = make_float4(0.f, 0.f, 0.f, 1.f);
-        if (m < p.M) {
-            float ci, co, cd, cu, ca;
-            gate_values(p.g, m, ci, co, cd, cu, ca);
-            const float cad = ca * cd;
-            sv.x = cad * ci;
-            sv.y = cad * co;
-            sv.z = ca * cu;
-            if (lead) st4(p.gates + m * 4, sv);
-        }
-        st4(&Sg[tid * 4], sv);
-    }
+    row_gate_prologue<BM>(p.g, m0, p.M, tid, lead, p.gates, Sg);
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     float4 ra[A_F4], ry[A_F4];
     uint4 rb[B_C][3];
     float bd[A_F4][3];
 #pragma unroll
     for (int q = 0; q < A_F4; ++q) bd[q][0] = bd[q][1] = bd[q][2] = 0.f;
-    const int64_t mlast = p.M - 1;
     const int64_t bsplit = (int64_t)p.N * p.F_out;  // elements per BT3 split
     auto fetch = [&](int k0) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const int idx = tid + NT * q;
-            const int64_t m = min(m0 + (idx >> 3), mlast);
-            const int k = k0 + 4 * (idx & 7);
-            const int kc = k < p.F_out ? k : 0;
-            ra[q] = ld4(p.dY + m * p.lddy + kc);
-            if (p.act) ry[q] = ld4(p.Y + m * p.ldy + kc);
-        }
+        a_fetch_f32<A_F4, NT, true>(p, m0, tid, k0, ra, ry);
 #pragma unroll
         for (int q = 0; q < B_C; ++q) {
             const int idx = tid + NT * q;
@@ -446,32 +528,9 @@ __global__ __launch_bounds__(64 * NW, 3) void dgrad_x3_kernel(DgradP p, const ui
         }
     };
     auto stash = [&](int buf, int k0) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const int idx = tid + NT * q;
-            const int k = k0 + 4 * (idx & 7);
-            const int64_t m = m0 + (idx >> 3);
-            float4 d = ra[q];
-            if (p.act) {
-                const float4 y = ry[q];
-                d.x = pg::act_grad(d.x, y.x, p.slope, p.drop_s);
-                d.y = pg::act_grad(d.y, y.y, p.slope, p.drop_s);
-                d.z = pg::act_grad(d.z, y.z, p.slope, p.drop_s);
-                d.w = pg::act_grad(d.w, y.w, p.slope, p.drop_s);
-            }
-            if (k >= p.F_out) d = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (lead && k < p.F_out && m < p.M) {
-                st4(p.dpre + m * p.ldp + k, d);
-#pragma unroll
-                for (int sg = 0; sg < 3; ++sg) bd[q][sg] += dot4(d, ld4(p.bsum + sg * p.F_out + k));
-            }
-            uint2 s0, s1, s2;
-            split4(d, s0, s1, s2);
-            const int o = (idx >> 3) * IMG + 4 * (idx & 7);
-            *reinterpret_cast<uint2*>(Aimg(buf, 0) + o) = s0;
-            *reinterpret_cast<uint2*>(Aimg(buf, 1) + o) = s1;
-            *reinterpret_cast<uint2*>(Aimg(buf, 2) + o) = s2;
-        }
+        a_stage_f32<A_F4, NT>(p, lead, m0, tid, k0, ra, ry, bd, [&](int idx, float4 d) {
+            split4_store(d, (idx >> 3) * IMG + 4 * (idx & 7), Aimg(buf, 0), Aimg(buf, 1), Aimg(buf, 2));
+        });
 #pragma unroll
         for (int q = 0; q < B_C; ++q) {
             const int idx = tid + NT * q;
@@ -527,85 +586,11 @@ __global__ __launch_bounds__(64 * NW, 3) void dgrad_x3_kernel(DgradP p, const ui
         __syncthreads();
     }
 
-    // bias dots <dpre[m], bsum_q>: 8 consecutive lanes hold one row's K slices
-    if (lead) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-#pragma unroll
-            for (int sg = 0; sg < 3; ++sg) {
-                float v = bd[q][sg];
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                bd[q][sg] = v;
-            }
-            const int idx = tid + NT * q;
-            if ((idx & 7) == 0) {
-                Bd[(idx >> 3) * 3 + 0] = bd[q][0];
-                Bd[(idx >> 3) * 3 + 1] = bd[q][1];
-                Bd[(idx >> 3) * 3 + 2] = bd[q][2];
-            }
-        }
-    }
-
+    if (lead) bias_dot_reduce<A_F4, NT>(bd, tid, Bd);
     float* T = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                T[rl * TLD + wn * TN * 32 + j * 32 + li] = acc[i][j][r];
-            }
+    acc_park(acc, T, TLD, wm * TM * 32, wn * TN * 32, 32, li, lh);
     __syncthreads();
-
-    constexpr int C4 = BN / 4;
-    constexpr int ITER = BM * C4 / NT;
-    constexpr int BATCH = ITER < 4 ? ITER : 4;
-    const int c4 = tid % C4;
-    const int j = n0 + 4 * c4;
-    const int seg = j < p.N ? j / p.F_in : 4;  // F_in % 4 == 0: a float4 never straddles segments
-    for (int it0 = 0; it0 < ITER; it0 += BATCH) {
-        float4 zv[BATCH];
-        int rl[BATCH];
-        int64_t mm[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            rl[u] = (tid + NT * (it0 + u)) / C4;
-            mm[u] = m0 + rl[u];
-            zv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (mm[u] < p.M && seg < 3) zv[u] = ld4(p.Z + mm[u] * p.ldz + j);
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            float part = 0.f;
-            if (mm[u] < p.M && seg < 4) {
-                const float4 gv = ld4(&T[rl[u] * TLD + 4 * c4]);
-                if (seg < 3) {
-                    const float sc = Sg[rl[u] * 4 + seg];
-                    if (p.dZ) st4(p.dZ + mm[u] * p.lddz + j, make_float4(sc * gv.x, sc * gv.y, sc * gv.z, sc * gv.w));
-                    part = dot4(gv, zv[u]);
-                } else {
-                    st4(p.dres + mm[u] * p.lddres + (j - 3 * p.F_in), gv);
-                }
-            }
-            T[rl[u] * TLD + 4 * c4] = part;  // own slot, already consumed
-        }
-    }
-    __syncthreads();
-    if (tid < BM && m0 + tid < p.M) {
-        const int64_t m = m0 + tid;
-        float ds[3] = {0.f, 0.f, 0.f};
-        if (lead) {
-            ds[0] = Bd[tid * 3 + 0];
-            ds[1] = Bd[tid * 3 + 1];
-            ds[2] = Bd[tid * 3 + 2];
-        }
-        row_gate_partials<C4>(&T[tid * TLD], n0, p.N, p.F_in, ds);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) p.dsp[((int64_t)nt * 3 + q) * p.M + m] = ds[q];
-    }
+    tile_epilogue_f32<BM, BN, NT, false>(p, T, Sg, Bd, lead, tid, m0, n0, nt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -626,7 +611,7 @@ struct SpanP {
 };
 
 template <int BM, int NW>
-__global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const uint16_t* BT3, SpanP sp) {
+__global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP<float> p, const uint16_t* BT3, SpanP sp) {
     constexpr int NT = 64 * NW;
     constexpr int WN = 2, WM = NW / WN;
     static_assert(BM == 32 * WM, "one 32-row MFMA tile per wave");
@@ -658,33 +643,10 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
     const int li = lane & 31, lh = lane >> 5;
     const int f = nt * FB + wn * 32 + li;  // this lane's feature (epilogue)
 
-    if (tid < BM) {
-        const int64_t m = m0 + tid;
-        float4 sv = make_float4(0.f, 0.f, 0.f, 1.f);
-        float w0 = 0.f, w1 = 0.f, w2 = 0.f;
-        if (m < p.M) {
-            float ci, co, cd, cu, ca;
-            gate_values(p.g, m, ci, co, cd, cu, ca);
-            const float cad = ca * cd;
-            sv.x = cad * ci;
-            sv.y = cad * co;
-            sv.z = ca * cu;
-            if (lead) st4(p.gates + m * 4, sv);
-            w0 = sp.wdiag[m * 3 + 0];
-            w1 = sp.wdiag[m * 3 + 1];
-            w2 = sp.wdiag[m * 3 + 2];
-        }
-        st4(&Sg[tid * 4], sv);
-        Wd[tid * 3 + 0] = w0;
-        Wd[tid * 3 + 1] = w1;
-        Wd[tid * 3 + 2] = w2;
-    }
+    row_gate_prologue<BM, true>(p.g, m0, p.M, tid, lead, p.gates, Sg, sp.wdiag, Wd);
 
-    f32x16 acc[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    f32x16 acc[1][3];  // one per segment
+    acc_zero(acc);
 
     float4 ra[A_F4], ry[A_F4];
     float bd[A_F4][3];
@@ -696,14 +658,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
     static_assert(B_C == 3, "three B pieces per thread");
     uint4 rb00, rb01, rb02, rb10, rb11, rb12, rb20, rb21, rb22;
     auto fetch = [&](int k0) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-            const int idx = tid + NT * q;
-            const int64_t m = min(m0 + (idx >> 3), mlast);
-            const int k = k0 + 4 * (idx & 7);
-            ra[q] = ld4(p.dY + m * p.lddy + k);
-            if (p.act) ry[q] = ld4(p.Y + m * p.ldy + k);
-        }
+        a_fetch_f32<A_F4, NT, false>(p, m0, tid, k0, ra, ry);
         // B (the split packed weights, 295 KB at F = 128: L2-resident), a k-tile ahead like A
         auto bsrc = [&](int q) {
             const int idx = tid + NT * q;
@@ -725,6 +680,8 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
         rb22 = *reinterpret_cast<const uint4*>(b2 + 2 * bsplit);
     };
     auto stash = [&](int k0) {
+        // a_stage_f32 without its k checks, kept as this kernel's own copy: through the shared template it took 214
+        // VGPRs instead of 216
 #pragma unroll
         for (int q = 0; q < A_F4; ++q) {
             const int idx = tid + NT * q;
@@ -764,7 +721,6 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
         *reinterpret_cast<uint4*>(Bimg(0) + o2) = rb20;
         *reinterpret_cast<uint4*>(Bimg(1) + o2) = rb21;
         *reinterpret_cast<uint4*>(Bimg(2) + o2) = rb22;
-        (void)k0;
     };
 
     const int ntiles = p.F_out / XBK;
@@ -787,12 +743,12 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
                                                                 8 * lh);
 #pragma unroll
             for (int j = 0; j < 3; ++j) {
-                acc[j] = mfma32_bf(a[2], b[j][0], acc[j]);
-                acc[j] = mfma32_bf(a[1], b[j][1], acc[j]);
-                acc[j] = mfma32_bf(a[0], b[j][2], acc[j]);
-                acc[j] = mfma32_bf(a[1], b[j][0], acc[j]);
-                acc[j] = mfma32_bf(a[0], b[j][1], acc[j]);
-                acc[j] = mfma32_bf(a[0], b[j][0], acc[j]);
+                acc[0][j] = mfma32_bf(a[2], b[j][0], acc[0][j]);
+                acc[0][j] = mfma32_bf(a[1], b[j][1], acc[0][j]);
+                acc[0][j] = mfma32_bf(a[0], b[j][2], acc[0][j]);
+                acc[0][j] = mfma32_bf(a[1], b[j][0], acc[0][j]);
+                acc[0][j] = mfma32_bf(a[0], b[j][1], acc[0][j]);
+                acc[0][j] = mfma32_bf(a[0], b[j][0], acc[0][j]);
             }
         }
         if (t + 1 < ntiles) {
@@ -802,25 +758,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
         __syncthreads();
     }
 
-    if (lead) {
-#pragma unroll
-        for (int q = 0; q < A_F4; ++q) {
-#pragma unroll
-            for (int sg = 0; sg < 3; ++sg) {
-                float v = bd[q][sg];
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                bd[q][sg] = v;
-            }
-            const int idx = tid + NT * q;
-            if ((idx & 7) == 0) {
-                Bd[(idx >> 3) * 3 + 0] = bd[q][0];
-                Bd[(idx >> 3) * 3 + 1] = bd[q][1];
-                Bd[(idx >> 3) * 3 + 2] = bd[q][2];
-            }
-        }
-    }
+    if (lead) bias_dot_reduce<A_F4, NT>(bd, tid, Bd);
 
     // epilogue through LDS: the accumulators are parked as T [BM][3 x 64] (the k-loop ended with a barrier); thread
     // item (row rl, features 4c..4c+3 of the block) reads G_q for q = in, out, und, writes dZ_q = s_q G_q and
@@ -846,13 +784,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
             yy[u] = p.act ? ld4(p.Y + m * p.ldy + fo) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            T[rl * TLD + j * FB + wn * 32 + li] = acc[j][r];
-        }
+    acc_park(acc, T, TLD, wm * 32, wn * 32, FB, li, lh);
     __syncthreads();
 #pragma unroll
     for (int u = 0; u < ITEMS; ++u) {
@@ -874,12 +806,7 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_span_kernel(DgradP p, const 
         }
         if (sp.e_res) {
             float4 d = dy[u];
-            if (p.act) {
-                d.x = pg::act_grad(d.x, yy[u].x, p.slope, p.drop_s);
-                d.y = pg::act_grad(d.y, yy[u].y, p.slope, p.drop_s);
-                d.z = pg::act_grad(d.z, yy[u].z, p.slope, p.drop_s);
-                d.w = pg::act_grad(d.w, yy[u].w, p.slope, p.drop_s);
-            }
+            if (p.act) d = act_grad4(d, yy[u], p.slope, p.drop_s);
             e = make_float4(e.x + d.x, e.y + d.y, e.z + d.z, e.w + d.w);
         }
         if (m < p.M) st4(sp.E + m * sp.lde + fo, e);
@@ -918,12 +845,17 @@ __global__ __launch_bounds__(256) void gate_grad_kernel(int64_t M, int ntn, cons
     }
 }
 
-// BT3[sp][c][r] = split sp of in[r][c] (the exact three-way bf16 split of pg_split3.h); R x C, once per backward
-__global__ __launch_bounds__(256) void transpose_split3_kernel(int R, int C, const float* in, uint16_t* out) {
-    const int64_t total = (int64_t)R * C;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i / R), r = (int)(i % R);
-        float v = in[(int64_t)r * C + c], fa, fb;
+// Per-element transforms of transpose_kernel: element i (of total) of the transposed matrix from the value v
+struct CopyElem {
+    template <typename T>
+    __device__ __forceinline__ void operator()(T v, T* out, int64_t i, int64_t) const {
+        out[i] = v;
+    }
+};
+// BT3[sp][c][r] = split sp of in[r][c] (the exact three-way bf16 split of pg_split3.h)
+struct Split3Elem {
+    __device__ __forceinline__ void operator()(float v, uint16_t* out, int64_t i, int64_t total) const {
+        float fa, fb;
         const uint32_t w0 = pgx3::bf2(v, 0.f, fa, fb);
         v -= fa;
         const uint32_t w1 = pgx3::bf2(v, 0.f, fa, fb);
@@ -933,37 +865,47 @@ __global__ __launch_bounds__(256) void transpose_split3_kernel(int R, int C, con
         out[total + i] = (uint16_t)(w1 & 0xffffu);
         out[2 * total + i] = (uint16_t)(w2 & 0xffffu);
     }
-}
+};
 
-__global__ __launch_bounds__(256) void transpose_kernel(int R, int C, const float* in, float* out) {
-    // out[c][r] = in[r][c]; tiny (the packed weights), run once per backward
+// out[c][r] = xf(in[r][c]) of an R x C matrix; tiny (the packed weights), run once per backward
+template <class Xf, typename In, typename Out>
+__global__ __launch_bounds__(256) void transpose_kernel(int R, int C, const In* in, Out* out) {
     const int64_t total = (int64_t)R * C;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
         const int c = (int)(i / R), r = (int)(i % R);
-        out[i] = in[(int64_t)r * C + c];
+        Xf{}(in[(int64_t)r * C + c], out, i, total);
     }
 }
+template <class Xf, typename In, typename Out>
+void launch_transpose(int R, int C, const In* in, Out* out, hipStream_t s) {
+    const int nb = (int)std::min<int64_t>(((int64_t)R * C + 255) / 256, 1024);
+    hipLaunchKernelGGL((transpose_kernel<Xf, In, Out>), dim3(nb), dim3(256), 0, s, R, C, in, out);
+}
 
+// E: the operands' element, float or uint16_t (bf16 bits)
+template <typename E>
 struct WgradP {
     int64_t M;
     int P, N, F_in;
-    const float* A;  // [M, P]
+    const E* A;  // [M, P] (dpre)
     int64_t lda;
-    const float* Z;  // segments 0..2
+    const E* Z;  // segments 0..2, [M, >= 3 F_in]
     int64_t ldz;
-    const float* R;  // segment 3 (projected residual input) or null
+    const E* R;  // segment 3 (projected residual input) or null
     int64_t ldr;
-    const float* gates;  // [M, 4] or null (all scales 1)
+    const float* gates;  // [M, 4]; fp32: or null (all scales 1)
     int64_t rows_per_split;
     int64_t part_stride;
     float* part;  // [splits, P*N + 4*P]
+    int col0;     // wgrad_bf16_kernel: first output column (the projected residual's columns after the staged
+                  // kernel's 3 F_in; then no bias sums here); unused by the fp32 kernels
 };
 
 constexpr int WROWS = 32;  // rows per K step
 constexpr int WLD = 132;   // LDS row (floats)
 
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void wgrad_kernel(WgradP p) {
+__global__ __launch_bounds__(64 * NW) void wgrad_kernel(WgradP<float> p) {
     constexpr int NT = 64 * NW;
     constexpr int BI = 128, BJ = 128;
     constexpr int WJ = 2, WI = NW / WJ;
@@ -1128,7 +1070,7 @@ __device__ __forceinline__ void wgrad_tile_of(int b, int tiles, int splits, int&
     if (split >= splits) tile = -1;
 }
 
-__global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgradP p, int splits) {
+__global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgradP<float> p, int splits) {
     __shared__ __attribute__((aligned(16))) uint4 U[2][3][2][WX_COLS];
     __shared__ float Db[2][4][WX_BP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, kh = lane >> 5;
@@ -1344,33 +1286,53 @@ void launch_reduce(int64_t n4, int splits, int64_t stride, const float* part, fl
 constexpr int BKB = 64;  // K per dgrad tile (4 MFMA k-steps)
 constexpr int LDKB = 72; // dgrad LDS row in bf16 (144 B: conflict-free ds_read_b128)
 
-struct DgradB {
-    int64_t M;
-    int F_in, F_out, N;
-    const uint16_t* dY;
-    int64_t lddy;
-    const uint16_t* Y;
-    int64_t ldy;
-    int act;
-    float slope;
-    float drop_s;        // fused layer dropout's scale (pg::act_grad), 0: none
-    const uint16_t* BT;  // [N, F_out] bf16
-    const float* bsum;   // [4, F_out]
-    const uint16_t* Z;
-    int64_t ldz;
-    Gates g;
-    uint16_t* dpre;
-    int64_t ldp;
-    uint16_t* dZ;
-    int64_t lddz;
-    uint16_t* dres;
-    int64_t lddres;
-    float* gates;
-    float* dsp;
-    int remap;
-    float* dpre32;  // optional fp32 copy of dpre (the rounded values), or null
-    int64_t ldp32;
-};
+// Non-temporal forms of the resident dgrad's once-touched streams: its dY / Y loads, its epilogue's Z loads and its
+// dZ stores. All three: config 5 3.904 -> 3.875 ms (mean of 3 interleaved runs, profiles/r06_ab_train_dgrad_nt.txt).
+typedef unsigned int pg_u4v __attribute__((ext_vector_type(4)));
+typedef unsigned int pg_u2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint4 ld16u(const uint16_t* q) {
+    const pg_u4v x = __builtin_nontemporal_load(reinterpret_cast<const pg_u4v*>(q));
+    return make_uint4(x.x, x.y, x.z, x.w);
+}
+__device__ __forceinline__ uint2 ld8u(const uint16_t* q) {
+    const pg_u2v x = __builtin_nontemporal_load(reinterpret_cast<const pg_u2v*>(q));
+    return make_uint2(x.x, x.y);
+}
+__device__ __forceinline__ void st8u(uint16_t* q, uint2 v) {
+    const pg_u2v x = {v.x, v.y};
+    __builtin_nontemporal_store(x, reinterpret_cast<pg_u2v*>(q));
+}
+
+// The bf16 A-piece stage (dgrad_bf16r_kernel; dgrad_bf16_kernel keeps its own copy, see there):
+// dpre of one fetched piece (row m, columns k..k+7), rounded to bf16; where `store` (a row below M of the lead n-tile)
+// it is written to dpre (and dpre32) and its bias dots are added to bd
+__device__ __forceinline__ uint4 a_piece_bf16(const DgradP<uint16_t>& p, uint4 ra, uint4 ry, int64_t m, int k,
+                                              bool store, float (&bd)[3]) {
+    float d[8];
+    pgbf::unpack8(ra, d);
+    if (p.act) {
+        float y[8];
+        pgbf::unpack8(ry, y);
+        act_grad8(d, y, p.slope, p.drop_s);
+    }
+    const uint4 v = pgbf::pack8(d);
+    if (store) {
+        *reinterpret_cast<uint4*>(p.dpre + m * p.ldp + k) = v;
+        float dr[8];
+        pgbf::unpack8(v, dr);  // the rounded gradient, as the products see it
+        if (p.dpre32) {
+            st4(p.dpre32 + m * p.ldp32 + k, make_float4(dr[0], dr[1], dr[2], dr[3]));
+            st4(p.dpre32 + m * p.ldp32 + k + 4, make_float4(dr[4], dr[5], dr[6], dr[7]));
+        }
+#pragma unroll
+        for (int sg = 0; sg < 3; ++sg) {
+            const float4 b0 = ld4(p.bsum + sg * p.F_out + k), b1 = ld4(p.bsum + sg * p.F_out + k + 4);
+            bd[sg] += dr[0] * b0.x + dr[1] * b0.y + dr[2] * b0.z + dr[3] * b0.w + dr[4] * b1.x + dr[5] * b1.y +
+                      dr[6] * b1.z + dr[7] * b1.w;
+        }
+    }
+    return v;
+}
 
 // Reproducibility (round 5). With packed-FP32 VALU math (v_pk_fma_f32 / v_pk_mul_f32, formed by the SLP vectoriser
 // from the lead tile's bias dots) this kernel's segment-0 gate partials came out wrong for 4-row groups (lanes 48-63
@@ -1380,7 +1342,7 @@ struct DgradB {
 // pg_dense_bwd.hip is therefore compiled with -fno-slp-vectorize (Makefile). The occupancy bound is 2 waves per SIMD
 // (154 VGPRs): at 4 (128 VGPRs) the compiler spilled 76 B per lane to scratch and the kernel ran 5 % slower.
 template <int BM, int BN, int NW>
-__global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradB p) {
+__global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradP<uint16_t> p) {
     using namespace pgbf;
     constexpr int NT = 64 * NW;
     constexpr int WN = 2, WM = NW / WN;
@@ -1409,28 +1371,10 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradB p) {
     const int wm = wave / WN, wn = wave % WN;
     const int li = lane & 31, lh = lane >> 5;
 
-    if (tid < BM) {
-        const int64_t m = m0 + tid;
-        float4 sv = make_float4(0.f, 0.f, 0.f, 1.f);
-        if (m < p.M) {
-            float ci, co, cd, cu, ca;
-            gate_values(p.g, m, ci, co, cd, cu, ca);
-            const float cad = ca * cd;
-            sv.x = cad * ci;
-            sv.y = cad * co;
-            sv.z = ca * cu;
-            if (lead) st4(p.gates + m * 4, sv);
-        }
-        st4(&Sg[tid * 4], sv);
-    }
+    row_gate_prologue<BM>(p.g, m0, p.M, tid, lead, p.gates, Sg);
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
 
     uint4 ra[A_C], ry[A_C], rb[B_C];
     float bd[A_C][3];
@@ -1464,14 +1408,15 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradB p) {
             const int k = k0 + 8 * (idx & 7);
             const int64_t m = m0 + (idx >> 3);
             uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            // a_piece_bf16, kept as this kernel's own copy: through the shared function it took 126 VGPRs (no scratch) at 4
+            // waves per SIMD instead of 148 at 3, a form nobody has timed
             if (k < p.F_out) {
                 float d[8];
                 unpack8(ra[q], d);
                 if (p.act) {
                     float y[8];
                     unpack8(ry[q], y);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) d[e] = pg::act_grad(d[e], y[e], p.slope, p.drop_s);
+                    act_grad8(d, y, p.slope, p.drop_s);
                 }
                 v = pack8(d);
                 if (lead && m < p.M) {
@@ -1531,38 +1476,12 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradB p) {
         __syncthreads();
     }
 
-    if (lead) {
-#pragma unroll
-        for (int q = 0; q < A_C; ++q) {
-#pragma unroll
-            for (int sg = 0; sg < 3; ++sg) {
-                float v = bd[q][sg];
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                bd[q][sg] = v;
-            }
-            const int idx = tid + NT * q;
-            if ((idx & 7) == 0) {
-                Bd[(idx >> 3) * 3 + 0] = bd[q][0];
-                Bd[(idx >> 3) * 3 + 1] = bd[q][1];
-                Bd[(idx >> 3) * 3 + 2] = bd[q][2];
-            }
-        }
-    }
-
+    if (lead) bias_dot_reduce<A_C, NT>(bd, tid, Bd);
     float* T = reinterpret_cast<float*>(smem);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = wm * TM * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                T[rl * TLD + wn * TN * 32 + j * 32 + li] = acc[i][j][r];
-            }
+    acc_park(acc, T, TLD, wm * TM * 32, wn * TN * 32, 32, li, lh);
     __syncthreads();
-
+    // The epilogue of dgrad_bf16r_kernel's, with Z loaded per batch of 4 items. Each kernel keeps its own copy: through
+    // one shared template this kernel's batch loop came out fully unrolled (90 vector-memory instructions instead of 74).
     constexpr int C4 = BN / 4;
     constexpr int ITER = BM * C4 / NT;
     constexpr int BATCH = ITER < 4 ? ITER : 4;
@@ -1602,23 +1521,8 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradB p) {
         for (int u = 0; u < BATCH; ++u) T[rl[u] * TLD + 4 * c4] = part[u];  // own slots
     }
     __syncthreads();
-    if (tid < BM && m0 + tid < p.M) {
-        const int64_t m = m0 + tid;
-        float ds[3] = {0.f, 0.f, 0.f};
-        if (lead) {
-            ds[0] = Bd[tid * 3 + 0];
-            ds[1] = Bd[tid * 3 + 1];
-            ds[2] = Bd[tid * 3 + 2];
-        }
-        for (int c = 0; c < C4; ++c) {
-            const int jj = n0 + 4 * c;
-            if (jj >= p.N) break;
-            const int q = jj / p.F_in;
-            if (q < 3) ds[q] += T[tid * TLD + 4 * c];
-        }  // (row_gate_partials spilled 16 B per lane here)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) p.dsp[((int64_t)nt * 3 + q) * p.M + m] = ds[q];
-    }
+    // the serial gate-partials loop: row_gate_partials spilled 16 B per lane here
+    row_dsp_store<BM, C4, true>(p, T, TLD, Bd, lead, tid, m0, n0, nt);
 }
 
 // Resident-A form of dgrad_bf16_kernel (round 5, the default where F_out <= 256 and F_out % 64 == 0): one 256-thread
@@ -1627,45 +1531,11 @@ __global__ __launch_bounds__(64 * NW, 2) void dgrad_bf16_kernel(DgradB p) {
 // n-tiles with the B k-tiles double-buffered a tile ahead (crossing n-tile boundaries) and the Z rows of each n-tile's
 // epilogue loaded during its last k-tile. Same products in the same order, same per-thread bias-dot order, same
 // epilogue: every output is bit-identical to dgrad_bf16_kernel's (PG_FLAG_DGRAD_BF16_TILED keeps that kernel).
-// diagnostics build only (-DPG_DGRAD_EXP=mask, tools/r06_dgrad_exp.sh): phases of dgrad_bf16r_kernel skipped
-#ifndef PG_DGRAD_EXP
-#define PG_DGRAD_EXP 0
-#endif
-#define GXP(bit) ((PG_DGRAD_EXP >> (bit)) & 1)
-// non-temporal forms of the resident dgrad's once-touched streams (PG_DGRAD_NT bits: 0 the dY / Y loads, 1 the
-// epilogue's Z loads, 2 its dZ stores); A/B builds via tools/r06_ab_lib2.sh
-#ifndef PG_DGRAD_NT
-#define PG_DGRAD_NT 7  // all three: config 5 3.904 -> 3.875 ms (mean of 3 interleaved runs, profiles/r06_ab_train_dgrad_nt.txt)
-#endif
-typedef unsigned int pg_u4v __attribute__((ext_vector_type(4)));
-typedef unsigned int pg_u2v __attribute__((ext_vector_type(2)));
-template <bool NT>
-__device__ __forceinline__ uint4 ld16u(const uint16_t* q) {
-    if constexpr (NT) {
-        const pg_u4v x = __builtin_nontemporal_load(reinterpret_cast<const pg_u4v*>(q));
-        return make_uint4(x.x, x.y, x.z, x.w);
-    }
-    return *reinterpret_cast<const uint4*>(q);
-}
-template <bool NT>
-__device__ __forceinline__ uint2 ld8u(const uint16_t* q) {
-    if constexpr (NT) {
-        const pg_u2v x = __builtin_nontemporal_load(reinterpret_cast<const pg_u2v*>(q));
-        return make_uint2(x.x, x.y);
-    }
-    return *reinterpret_cast<const uint2*>(q);
-}
-template <bool NT>
-__device__ __forceinline__ void st8u(uint16_t* q, uint2 v) {
-    if constexpr (NT) {
-        const pg_u2v x = {v.x, v.y};
-        __builtin_nontemporal_store(x, reinterpret_cast<pg_u2v*>(q));
-    } else {
-        *reinterpret_cast<uint2*>(q) = v;
-    }
-}
+// Its once-touched streams (dY / Y, the epilogue's Z, dZ) are non-temporal (ld16u, ld8u, st8u); its gate dots come
+// before its stores and its B load is unconditional (see below). The phase times quoted in this kernel's comments were
+// measured with a phase-skipping diagnostics build that has since been removed (profiles/r06_dgrad_exp.txt).
 constexpr int RB_BM = 64, RB_NW = 4, RB_FMAX = 256;
-__global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
+__global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradP<uint16_t> p) {
     using namespace pgbf;
     constexpr int BM = RB_BM, BN = 128, NW = RB_NW, NT = 64 * NW;
     constexpr int WN = 2, WM = NW / WN;
@@ -1695,20 +1565,7 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
     const int li = lane & 31, lh = lane >> 5;
     const int64_t mlast = p.M - 1;
 
-    if (tid < BM) {
-        const int64_t m = m0 + tid;
-        float4 sv = make_float4(0.f, 0.f, 0.f, 1.f);
-        if (m < p.M) {
-            float ci, co, cd, cu, ca;
-            gate_values(p.g, m, ci, co, cd, cu, ca);
-            const float cad = ca * cd;
-            sv.x = cad * ci;
-            sv.y = cad * co;
-            sv.z = ca * cu;
-            st4(p.gates + m * 4, sv);
-        }
-        st4(&Sg[tid * 4], sv);
-    }
+    row_gate_prologue<BM>(p.g, m0, p.M, tid, true, p.gates, Sg);  // owns every n-tile of its rows: no lead test
 
     // B k-tile g = nt * KT + kt -> registers, two tiles ahead in two named sets (an array of registers here stays in
     // scratch memory): tile g + 1 waits in one set while tile g + 2 loads into the other
@@ -1725,10 +1582,6 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
             return reinterpret_cast<const uint4*>(p.BT + (int64_t)n * p.F_out + k0 + 8 * (idx & 7));
         };
         B4 r;
-        if (GXP(1)) {
-            r.a = r.b = r.c = r.d = make_uint4(g, tid, 0u, 0u);
-            return r;
-        }
         r.a = *src(0);
         r.b = *src(1);
         r.c = *src(2);
@@ -1758,13 +1611,8 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
                 const int idx = tid + NT * q;
                 const int64_t m = min(m0 + (idx >> 3), mlast);
                 const int k = (t < KT ? t : 0) * BKB + 8 * (idx & 7);
-                if (GXP(5)) {
-                    ra[t][q] = make_uint4(m, k, 0u, 0u);
-                    ry[t][q] = ra[t][q];
-                    continue;
-                }
-                ra[t][q] = ld16u<(PG_DGRAD_NT & 1) != 0>(p.dY + m * p.lddy + k);
-                if (p.act) ry[t][q] = ld16u<(PG_DGRAD_NT & 1) != 0>(p.Y + m * p.ldy + k);
+                ra[t][q] = ld16u(p.dY + m * p.lddy + k);
+                if (p.act) ry[t][q] = ld16u(p.Y + m * p.ldy + k);
             }
         S0 = loadB(0);
         float bd[A_C][3];
@@ -1778,50 +1626,11 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
                 const int idx = tid + NT * q;
                 const int k = t * BKB + 8 * (idx & 7);
                 const int64_t m = m0 + (idx >> 3);
-                float d[8];
-                unpack8(ra[t][q], d);
-                if (p.act) {
-                    float y[8];
-                    unpack8(ry[t][q], y);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) d[e] = pg::act_grad(d[e], y[e], p.slope, p.drop_s);
-                }
-                const uint4 v = pack8(d);
-                if (m < p.M) {
-                    if (!GXP(2)) *reinterpret_cast<uint4*>(p.dpre + m * p.ldp + k) = v;
-                    float dr[8];
-                    unpack8(v, dr);
-                    if (p.dpre32 && !GXP(2)) {
-                        st4(p.dpre32 + m * p.ldp32 + k, make_float4(dr[0], dr[1], dr[2], dr[3]));
-                        st4(p.dpre32 + m * p.ldp32 + k + 4, make_float4(dr[4], dr[5], dr[6], dr[7]));
-                    }
-#pragma unroll
-                    for (int sg = 0; sg < 3; ++sg) {
-                        const float4 b0 = ld4(p.bsum + sg * p.F_out + k), b1 = ld4(p.bsum + sg * p.F_out + k + 4);
-                        bd[q][sg] += dr[0] * b0.x + dr[1] * b0.y + dr[2] * b0.z + dr[3] * b0.w + dr[4] * b1.x +
-                                     dr[5] * b1.y + dr[6] * b1.z + dr[7] * b1.w;
-                    }
-                }
-                *reinterpret_cast<uint4*>(&As[(idx >> 3) * LDA + k]) = v;
+                *reinterpret_cast<uint4*>(&As[(idx >> 3) * LDA + k]) =
+                    a_piece_bf16(p, ra[t][q], ry[t][q], m, k, m < p.M, bd[q]);
             }
         }
-#pragma unroll
-        for (int q = 0; q < A_C; ++q) {
-#pragma unroll
-            for (int sg = 0; sg < 3; ++sg) {
-                float v = bd[q][sg];
-                v += __shfl_xor(v, 1);
-                v += __shfl_xor(v, 2);
-                v += __shfl_xor(v, 4);
-                bd[q][sg] = v;
-            }
-            const int idx = tid + NT * q;
-            if ((idx & 7) == 0) {
-                Bd[(idx >> 3) * 3 + 0] = bd[q][0];
-                Bd[(idx >> 3) * 3 + 1] = bd[q][1];
-                Bd[(idx >> 3) * 3 + 2] = bd[q][2];
-            }
-        }
+        bias_dot_reduce<A_C, NT>(bd, tid, Bd);
     }
     const int G = ntn * KT;
     if (G > 1) S1 = loadB(1);
@@ -1829,20 +1638,14 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
     __syncthreads();
 
     const int c4 = tid % C4;
-    f32x16 acc[TN];
+    f32x16 acc[TM][TN];
     uint2 zv[ITER];
     auto epilogue = [&](int nt) __attribute__((always_inline)) {  // the B buffers are free: T aliases them
+        acc_park(acc, T, TLD, wm * 32, wn * TN * 32, 32, li, lh);
+        __syncthreads();
         const int n0 = nt * BN;
         const int j = n0 + 4 * c4;
         const int seg = j < p.N ? j / p.F_in : 4;
-#pragma unroll
-        for (int jj = 0; jj < TN; ++jj)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                T[rl * TLD + wn * TN * 32 + jj * 32 + li] = acc[jj][r];
-            }
-        __syncthreads();
         // the gate dots first: every use of the Z rows precedes this epilogue's stores, so the compiler waits for
         // the Z loads once; with a dot after each dZ store it drained the whole memory queue (vmcnt(0): the stores
         // and the next B k-tile) at every one of the 8 items. Same products and order: the same bits.
@@ -1861,10 +1664,9 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
                 const float4 gv = ld4(&T[rl * TLD + 4 * c4]);
                 if (seg < 3) {
                     const float sc = Sg[rl * 4 + seg];
-                    if (p.dZ && !GXP(0))
-                        st8u<(PG_DGRAD_NT & 4) != 0>(p.dZ + mm * p.lddz + j,
-                                                     pack4(make_float4(sc * gv.x, sc * gv.y, sc * gv.z, sc * gv.w)));
-                } else if (!GXP(0)) {
+                    if (p.dZ)
+                        st8u(p.dZ + mm * p.lddz + j, pack4(make_float4(sc * gv.x, sc * gv.y, sc * gv.z, sc * gv.w)));
+                } else {
                     *reinterpret_cast<uint2*>(p.dres + mm * p.lddres + (j - 3 * p.F_in)) = pack4(gv);
                 }
             }
@@ -1872,38 +1674,14 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
 #pragma unroll
         for (int u = 0; u < ITER; ++u) T[((tid + NT * u) / C4) * TLD + 4 * c4] = part[u];  // own slots
         __syncthreads();
-        if (tid < BM && m0 + tid < p.M && !GXP(7)) {
-            const int64_t m = m0 + tid;
-            float ds[3] = {0.f, 0.f, 0.f};
-            if (nt == 0) {
-                ds[0] = Bd[tid * 3 + 0];
-                ds[1] = Bd[tid * 3 + 1];
-                ds[2] = Bd[tid * 3 + 2];
-            }
-            row_gate_partials<C4>(&T[tid * TLD], n0, p.N, p.F_in, ds);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) p.dsp[((int64_t)nt * 3 + q) * p.M + m] = ds[q];
-        }
+        row_dsp_store<BM, C4, false>(p, T, TLD, Bd, nt == 0, tid, m0, n0, nt);
         __syncthreads();  // T is read before the next n-tile's first B k-tile overwrites it
-    };
-    auto acc_sink = [&](int nt) __attribute__((always_inline)) {  // diagnostics: keep the products live
-        float t = 0.f;
-#pragma unroll
-        for (int jj = 0; jj < TN; ++jj)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) t += acc[jj][r];
-        if (t == 12345.f) p.dsp[nt] = t;
     };
     // tile g: MFMAs on buffer g & 1 (tile g, stashed); tile g + 2 loads into one register set while tile g + 1 goes
     // from the other to the other buffer -- after the epilogue when g ends an n-tile (even g: load S0, stash S1)
     auto step = [&](int g, auto odd) __attribute__((always_inline)) {  // odd: tile g + 2 loads into S1, g + 1 is in S0
         const int nt = g / KT, kt = g - nt * KT;
-        if (kt == 0) {
-#pragma unroll
-            for (int jj = 0; jj < TN; ++jj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[jj][r] = 0.f;
-        }
+        if (kt == 0) acc_zero(acc);
         {  // unconditional (the last steps re-read tile G - 1, unused): with a load on every path the compiler's
            // wait before the stash below counts the 4 younger loads (vmcnt(4)) instead of draining everything,
            // epilogue stores included (vmcnt(0)), at every k-tile
@@ -1917,7 +1695,7 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
 #pragma unroll
             for (int u = 0; u < ITER; ++u) {
                 const int64_t m = min(m0 + (tid + NT * u) / C4, mlast);
-                zv[u] = zseg && !GXP(6) ? ld8u<(PG_DGRAD_NT & 2) != 0>(p.Z + m * p.ldz + j) : make_uint2(m, j);
+                zv[u] = zseg ? ld8u(p.Z + m * p.ldz + j) : make_uint2(m, j);  // (past the gated segments: unused)
             }
         }
         const uint16_t* Bb = Bs + (g & 1) * BN * LDKB;
@@ -1931,10 +1709,8 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
                 b[jj] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(
                                                       &Bb[(wn * TN * 32 + jj * 32 + li) * LDKB + kk * 16 + 8 * lh]));
 #pragma unroll
-            for (int jj = 0; jj < TN; ++jj) {
-                if (GXP(3)) acc[jj][kk] += (float)a[jj] * (float)b[jj][kk];
-                else acc[jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[jj], acc[jj], 0, 0, 0);
-            }
+            for (int jj = 0; jj < TN; ++jj)
+                acc[0][jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b[jj], acc[0][jj], 0, 0, 0);
         }
         auto stash_next = [&]() __attribute__((always_inline)) {
             if constexpr (decltype(odd)::value) stashB(S0, (g + 1) & 1);
@@ -1945,8 +1721,7 @@ __global__ __launch_bounds__(64 * RB_NW, 2) void dgrad_bf16r_kernel(DgradB p) {
             __syncthreads();
         } else {
             __syncthreads();
-            if (!GXP(4)) epilogue(nt);
-            else acc_sink(nt);
+            epilogue(nt);
             if (g + 1 < G) {
                 stash_next();
                 __syncthreads();
@@ -1990,23 +1765,6 @@ __global__ __launch_bounds__(256) void grads_layout_kernel(int F_out, int F_in, 
     }
 }
 
-struct WgradB {
-    int64_t M;
-    int P, N, F_in;
-    const uint16_t* A;  // dpre [M, P] bf16
-    int64_t lda;
-    const uint16_t* Z;  // [M, >= 3 F_in] bf16
-    int64_t ldz;
-    const uint16_t* R;  // segment 3 (projected residual input) bf16, or null
-    int64_t ldr;
-    const float* gates; // [M, 4]
-    int64_t rows_per_split;
-    int64_t part_stride;
-    float* part;
-    int col0;           // wgrad_bf16_kernel: first output column (the projected residual's columns after the staged
-                        // kernel's 3 F_in; then no bias sums here)
-};
-
 constexpr int WRB = 32;  // rows per K step (2 MFMA k-steps)
 constexpr int LDM = 40;  // transposed LDS row in bf16: 32 rows + 8 pad (80 B: conflict-free ds_read_b128)
 
@@ -2014,7 +1772,7 @@ constexpr int LDM = 40;  // transposed LDS row in bf16: 32 rows + 8 pad (80 B: c
 // row), so each MFMA operand (8 consecutive K = rows) is one ds_read_b128. Waves 0-3 stage A (and sum
 // the bias gradients), waves 4-7 stage s*B; a thread owns a row pair x 8 columns and writes each column's
 // two rows as one 32-bit LDS word.
-__global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradB p) {
+__global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradP<uint16_t> p) {
     using namespace pgbf;
     constexpr int BI = 128, BJ = 128;
     __shared__ __attribute__((aligned(16))) uint16_t At[2][BI * LDM];
@@ -2150,14 +1908,6 @@ __global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradB p) {
     }
 }
 
-__global__ __launch_bounds__(256) void transpose_u16_kernel(int R, int C, const uint16_t* in, uint16_t* out) {
-    const int64_t total = (int64_t)R * C;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i / R), r = (int)(i % R);
-        out[i] = in[(int64_t)r * C + c];
-    }
-}
-
 constexpr int DG_BM = 128, DG_BN = 128, DG_NW = 8, WG_NW = 8;
 constexpr int X3_BM = 64, X3_NW = 4;  // dgrad_x3_kernel: 64-row blocks of 4 waves, three workgroups per CU
 
@@ -2197,7 +1947,7 @@ SplitPlan split_rows(int64_t M, int64_t tiles) {
 // 128-column tile: 984 MB at F = 256 against the 656 MB here.
 constexpr int WB_K = 32;  // rows per step (4 k-groups of 8)
 
-__global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradB p, int splits) {
+__global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, int splits) {
     __shared__ __attribute__((aligned(16))) uint4 U[2][4][WX_COLS];
     __shared__ float Db[4][4][WX_BP];
     __shared__ float Gs[2][3][WB_K];
@@ -2374,7 +2124,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradB p, int splits)
 constexpr int GEN_MAX_FOUT = 8192;  // dpre row staged in LDS
 
 // one 256-thread block per row (grid-stride): dpre, gates, dZ / dres, and ds_q into dsp tile 0
-__global__ __launch_bounds__(256) void dgrad_generic_kernel(DgradP p) {
+__global__ __launch_bounds__(256) void dgrad_generic_kernel(DgradP<float> p) {
     __shared__ float dp[GEN_MAX_FOUT];
     __shared__ float red[3][256];
     const int tid = threadIdx.x;
@@ -2519,11 +2269,10 @@ int64_t pg_directgcn_dense_bwd_workspace(const pg_layer_args_t* a) {
 }  // extern "C"
 
 namespace {
-// the fp32 backward; span != nullptr: pg_directgcn_dense_bwd_span_f32 (dgrad_span_kernel, E = diagonal term of the
-// transposed propagation (+ residual), PG_ERR_UNSUPPORTED unless its shape conditions hold)
-int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_layer_grad_args_t* g, uint32_t flags,
-                       void* stream, const SpanP* span) {
-    PG_REQUIRE(a != nullptr && packed != nullptr && g != nullptr, "null args");
+// The fp32 and bf16 entry points' shared argument checks (packed_ok: the entry point's packed weight pointers are
+// non-null) and the fused dropout's scale
+int bwd_check_args(const pg_layer_args_t* a, bool packed_ok, const pg_layer_grad_args_t* g, float& drop_s) {
+    PG_REQUIRE(a != nullptr && packed_ok && g != nullptr, "null args");
     PG_REQUIRE(a->M >= 0 && a->F_in > 0 && a->F_out > 0 && a->F_in < (1 << 20) && a->F_out < (1 << 20),
                "bad shape M=%lld F_in=%lld F_out=%lld", (long long)a->M, (long long)a->F_in, (long long)a->F_out);
     PG_REQUIRE(a->C_in && a->C_out && a->C_directed && a->C_undirected && a->C_all, "null gate");
@@ -2533,8 +2282,81 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
     PG_REQUIRE(!a->act || a->Y, "act needs the forward output Y");
     PG_REQUIRE(!a->W_res || g->dres, "W_res needs dres");
     uint32_t drop_thr = 0;
+    return pg::drop_params(a, drop_thr, drop_s, false);
+}
+
+// no rows: all parameter gradients are zero (after the entry point's own layout checks; fn: the public function called)
+int bwd_no_rows(const char* fn, const pg_layer_grad_args_t* g, int64_t F_out, int64_t K, hipStream_t s) {
+    if (hipMemsetAsync(g->dW, 0, sizeof(float) * (F_out * K + 4 * F_out), s) != hipSuccess)
+        return pg::set_error(PG_ERR_HIP, "%s: memset failed", fn);
+    return PG_OK;
+}
+
+// the dgrad kernels' arguments; E = uint16_t: the ABI's float pointers hold bf16 bits. BT: the transposed packed
+// weights in the workspace
+template <typename E>
+DgradP<E> dgrad_params(const pg_layer_args_t* a, const float* packed, const pg_layer_grad_args_t* g, const BwdPlan& pl,
+                       const Gates& gt, float drop_s, uint32_t flags) {
+    DgradP<E> p{};
+    p.M = a->M;
+    p.F_in = (int)a->F_in;
+    p.F_out = (int)a->F_out;
+    p.N = pl.K;
+    p.dY = reinterpret_cast<const E*>(g->dY);
+    p.lddy = g->lddy;
+    p.Y = reinterpret_cast<const E*>(a->Y);
+    p.ldy = a->ldy;
+    p.act = a->act;
+    p.slope = a->slope;
+    p.drop_s = drop_s;
+    p.BT = reinterpret_cast<const E*>(g->work + pl.off_bt);
+    p.bsum = packed + a->F_out * pl.K;
+    p.Z = reinterpret_cast<const E*>(a->Z);
+    p.ldz = a->ldz;
+    p.g = gt;
+    p.dpre = reinterpret_cast<E*>(g->dpre);
+    p.ldp = g->ldp;
+    p.dZ = reinterpret_cast<E*>(g->dZ);
+    p.lddz = g->lddz;
+    p.dres = reinterpret_cast<E*>(g->dres);
+    p.lddres = g->lddres;
+    p.gates = g->gates;
+    p.dsp = g->work + pl.off_dsp;
+    p.remap = (flags & PG_FLAG_NO_XCD_REMAP) ? 0 : 1;
+    if (std::is_same<E, uint16_t>::value) {
+        p.dpre32 = g->dpre_f32;
+        p.ldp32 = g->ldp_f32;
+    }
+    return p;
+}
+
+// the layer's wgrad kernels' arguments (A = dpre, B = the gated Z segments and the projected residual's input)
+template <typename E>
+WgradP<E> wgrad_params(const pg_layer_args_t* a, const pg_layer_grad_args_t* g, const BwdPlan& pl) {
+    WgradP<E> w{};
+    w.M = a->M;
+    w.P = (int)a->F_out;
+    w.N = pl.K;
+    w.F_in = (int)a->F_in;
+    w.A = reinterpret_cast<const E*>(g->dpre);
+    w.lda = g->ldp;
+    w.Z = reinterpret_cast<const E*>(a->Z);
+    w.ldz = a->ldz;
+    w.R = reinterpret_cast<const E*>(a->res_x);
+    w.ldr = a->ld_res;
+    w.gates = g->gates;
+    w.rows_per_split = pl.rows_per_split;
+    w.part_stride = pl.part_stride;
+    w.part = g->work + pl.off_part;
+    return w;
+}
+
+// the fp32 backward; span != nullptr: pg_directgcn_dense_bwd_span_f32 (dgrad_span_kernel, E = diagonal term of the
+// transposed propagation (+ residual), PG_ERR_UNSUPPORTED unless its shape conditions hold)
+int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_layer_grad_args_t* g, uint32_t flags,
+                       void* stream, const SpanP* span) {
     float drop_s = 0.f;
-    if (const int rc = pg::drop_params(a, drop_thr, drop_s, false)) return rc;
+    if (const int rc = bwd_check_args(a, packed != nullptr, g, drop_s)) return rc;
     const bool proj = a->W_res != nullptr;
     const bool x3w = wgrad_x3_shape(a->F_in, a->F_out, proj) && !(flags & PG_FLAG_WGRAD_F32MFMA);
     const BwdPlan pl = plan_of(a->M, a->F_in, a->F_out, proj, x3w);
@@ -2555,15 +2377,10 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
     hipStream_t s = (hipStream_t)stream;
     const int K = pl.K;
     const int F_in = (int)a->F_in, F_out = (int)a->F_out;
-    float* work = g->work;
-    float* BT = work + pl.off_bt;
-    float* dsp = work + pl.off_dsp;
-    float* part = work + pl.off_part;
-    if (a->M == 0) {  // no rows: all parameter gradients are zero
-        if (hipMemsetAsync(g->dW, 0, sizeof(float) * ((int64_t)F_out * K + 4 * F_out), s) != hipSuccess)
-            return pg::set_error(PG_ERR_HIP, "pg_directgcn_dense_bwd_f32: memset failed");
-        return PG_OK;
-    }
+    float* BT = g->work + pl.off_bt;
+    float* dsp = g->work + pl.off_dsp;
+    float* part = g->work + pl.off_part;
+    if (a->M == 0) return bwd_no_rows("pg_directgcn_dense_bwd_f32", g, F_out, K, s);
     // the split-bf16 dgrad where the k-tiles are whole (F_out % 32 == 0); PG_FLAG_DGRAD_F32MFMA keeps the fp32 MFMAs
     const bool x3 = vec && a->F_out % XBK == 0 && (span || !(flags & PG_FLAG_DGRAD_F32MFMA));
     if (span) {
@@ -2575,39 +2392,11 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
                                  "F_in == F_out with e_res");
     }
     uint16_t* BT3 = reinterpret_cast<uint16_t*>(BT);
-    {
-        const int64_t total = (int64_t)K * F_out;
-        const int nb = (int)std::min<int64_t>((total + 255) / 256, 1024);
-        if (x3) hipLaunchKernelGGL(transpose_split3_kernel, dim3(nb), dim3(256), 0, s, F_out, K, packed, BT3);
-        else hipLaunchKernelGGL(transpose_kernel, dim3(nb), dim3(256), 0, s, F_out, K, packed, BT);
-    }
+    if (x3) launch_transpose<Split3Elem>(F_out, K, packed, BT3, s);
+    else launch_transpose<CopyElem>(F_out, K, packed, BT, s);
     Gates gt{a->gate_mode, a->C_in, a->C_out, a->C_directed, a->C_undirected, a->C_all, a->rows};
+    const DgradP<float> p = dgrad_params<float>(a, packed, g, pl, gt, drop_s, flags);
     if (!vec) {  // any shape: per-element kernels (same outputs, sums in another order)
-        DgradP p{};
-        p.M = a->M;
-        p.F_in = F_in;
-        p.F_out = F_out;
-        p.N = K;
-        p.dY = g->dY;
-        p.lddy = g->lddy;
-        p.Y = a->Y;
-        p.ldy = a->ldy;
-        p.act = a->act;
-        p.slope = a->slope;
-        p.drop_s = drop_s;
-        p.BT = BT;
-        p.bsum = packed + (int64_t)F_out * K;
-        p.Z = a->Z;
-        p.ldz = a->ldz;
-        p.g = gt;
-        p.dpre = g->dpre;
-        p.ldp = g->ldp;
-        p.dZ = g->dZ;
-        p.lddz = g->lddz;
-        p.dres = g->dres;
-        p.lddres = g->lddres;
-        p.gates = g->gates;
-        p.dsp = dsp;
         const unsigned nb = (unsigned)std::min<int64_t>(a->M, 8192);
         hipLaunchKernelGGL(dgrad_generic_kernel, dim3(nb), dim3(256), 0, s, p);
         const int gb = (int)std::min<int64_t>((a->M + 255) / 256, 2048);
@@ -2636,32 +2425,6 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
         return pg::check_launch("pg_directgcn_dense_bwd_f32");
     }
     {
-        DgradP p{};
-        p.M = a->M;
-        p.F_in = F_in;
-        p.F_out = F_out;
-        p.N = K;
-        p.dY = g->dY;
-        p.lddy = g->lddy;
-        p.Y = a->Y;
-        p.ldy = a->ldy;
-        p.act = a->act;
-        p.slope = a->slope;
-        p.drop_s = drop_s;
-        p.BT = BT;
-        p.bsum = packed + (int64_t)F_out * K;
-        p.Z = a->Z;
-        p.ldz = a->ldz;
-        p.g = gt;
-        p.dpre = g->dpre;
-        p.ldp = g->ldp;
-        p.dZ = g->dZ;
-        p.lddz = g->lddz;
-        p.dres = g->dres;
-        p.lddres = g->lddres;
-        p.gates = g->gates;
-        p.dsp = dsp;
-        p.remap = (flags & PG_FLAG_NO_XCD_REMAP) ? 0 : 1;
         const int64_t nb = ((a->M + DG_BM - 1) / DG_BM) * pl.ntn;
         if (span)
             hipLaunchKernelGGL((dgrad_span_kernel<X3_BM, X3_NW>),
@@ -2678,21 +2441,7 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
                            (const float*)dsp, gt, g->dgate);
     }
     {
-        WgradP w{};
-        w.M = a->M;
-        w.P = F_out;
-        w.N = K;
-        w.F_in = F_in;
-        w.A = g->dpre;
-        w.lda = g->ldp;
-        w.Z = a->Z;
-        w.ldz = a->ldz;
-        w.R = a->res_x;
-        w.ldr = a->ld_res;
-        w.gates = g->gates;
-        w.rows_per_split = pl.rows_per_split;
-        w.part_stride = pl.part_stride;
-        w.part = part;
+        const WgradP<float> w = wgrad_params<float>(a, g, pl);
         if (x3w) {
             const int tiles = (F_out / WX_BP) * (K / WX_BN);
             hipLaunchKernelGGL(wgrad_x3_kernel, dim3((unsigned)(8 * ((pl.splits + 7) / 8) * tiles)), dim3(512), 0, s, w,
@@ -2763,7 +2512,7 @@ int pg_gemm_at_b_f32(int64_t M, int64_t P, int64_t N, const float* A, int64_t ld
     const int64_t stride = up4(P * N + 4 * P);
     PG_REQUIRE(work_floats >= (int64_t)sp.splits * stride, "workspace too small: %lld < %lld floats",
                (long long)work_floats, (long long)sp.splits * stride);
-    WgradP w{};
+    WgradP<float> w{};
     w.M = M;
     w.P = (int)P;
     w.N = (int)N;
@@ -2786,17 +2535,8 @@ int pg_gemm_at_b_f32(int64_t M, int64_t P, int64_t N, const float* A, int64_t ld
 
 int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, const uint16_t* packed_bf16,
                                 const pg_layer_grad_args_t* g, uint32_t flags, void* stream) {
-    PG_REQUIRE(a != nullptr && packed != nullptr && packed_bf16 != nullptr && g != nullptr, "null args");
-    PG_REQUIRE(a->M >= 0 && a->F_in > 0 && a->F_out > 0 && a->F_in < (1 << 20) && a->F_out < (1 << 20), "bad shape");
-    PG_REQUIRE(a->C_in && a->C_out && a->C_directed && a->C_undirected && a->C_all, "null gate");
-    PG_REQUIRE(a->gate_mode == PG_GATES_VECTOR || a->gate_mode == PG_GATES_SCALAR, "bad gate_mode");
-    PG_REQUIRE(!a->W_res || a->res_x, "W_res needs res_x");
-    PG_REQUIRE(g->dY && g->dpre && g->dgate && g->gates && g->dW && g->work, "null gradient buffer");
-    PG_REQUIRE(!a->act || a->Y, "act needs the forward output Y");
-    PG_REQUIRE(!a->W_res || g->dres, "W_res needs dres");
-    uint32_t drop_thr = 0;
     float drop_s = 0.f;
-    if (const int rc = pg::drop_params(a, drop_thr, drop_s, false)) return rc;
+    if (const int rc = bwd_check_args(a, packed != nullptr && packed_bf16 != nullptr, g, drop_s)) return rc;
     const bool proj = a->W_res != nullptr;
     // the staged weight gradient (wgrad_bfs_kernel) where its tiles fit; PG_FLAG_WGRAD_BF16_TILED keeps the 128 x 128
     // tiles of wgrad_bf16_kernel
@@ -2830,49 +2570,13 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
     hipStream_t s = (hipStream_t)stream;
     const int K = pl.K;
     const int F_in = (int)a->F_in, F_out = (int)a->F_out;
-    if (a->M == 0) {
-        if (hipMemsetAsync(g->dW, 0, sizeof(float) * ((int64_t)F_out * K + 4 * F_out), s) != hipSuccess)
-            return pg::set_error(PG_ERR_HIP, "pg_directgcn_dense_bwd_bf16: memset failed");
-        return PG_OK;
-    }
-    uint16_t* BT = reinterpret_cast<uint16_t*>(g->work + pl.off_bt);
+    if (a->M == 0) return bwd_no_rows("pg_directgcn_dense_bwd_bf16", g, F_out, K, s);
     float* dsp = g->work + pl.off_dsp;
     float* part = g->work + pl.off_part;
-    {
-        const int64_t total = (int64_t)K * F_out;
-        const int nb = (int)std::min<int64_t>((total + 255) / 256, 1024);
-        hipLaunchKernelGGL(transpose_u16_kernel, dim3(nb), dim3(256), 0, s, F_out, K, packed_bf16, BT);
-    }
+    launch_transpose<CopyElem>(F_out, K, packed_bf16, reinterpret_cast<uint16_t*>(g->work + pl.off_bt), s);
     Gates gt{a->gate_mode, a->C_in, a->C_out, a->C_directed, a->C_undirected, a->C_all, a->rows};
     {
-        DgradB p{};
-        p.M = a->M;
-        p.F_in = F_in;
-        p.F_out = F_out;
-        p.N = K;
-        p.dY = dYb;
-        p.lddy = g->lddy;
-        p.Y = Yb;
-        p.ldy = a->ldy;
-        p.act = a->act;
-        p.slope = a->slope;
-        p.drop_s = drop_s;
-        p.BT = BT;
-        p.bsum = packed + (int64_t)F_out * K;
-        p.Z = Zb;
-        p.ldz = a->ldz;
-        p.g = gt;
-        p.dpre = dpb;
-        p.ldp = g->ldp;
-        p.dZ = dZb;
-        p.lddz = g->lddz;
-        p.dres = drb;
-        p.lddres = g->lddres;
-        p.gates = g->gates;
-        p.dsp = dsp;
-        p.remap = (flags & PG_FLAG_NO_XCD_REMAP) ? 0 : 1;
-        p.dpre32 = g->dpre_f32;
-        p.ldp32 = g->ldp_f32;
+        const DgradP<uint16_t> p = dgrad_params<uint16_t>(a, packed, g, pl, gt, drop_s, flags);
         // resident-A kernel: 64-row workgroups, two per CU; below 256 rows per CU (a P = 8 rank's 20,000 rows: 313
         // workgroups) they underfill the GPU and the per-n-tile kernel's N / 128 times as many workgroups run faster
         int dev = 0, ncu = 256;
@@ -2894,27 +2598,13 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
         hipLaunchKernelGGL(gate_grad_kernel, dim3(nb), dim3(256), 0, s, a->M, pl.ntn, (const float*)dsp, gt, g->dgate);
     }
     {
-        WgradB w{};
-        w.M = a->M;
-        w.P = F_out;
-        w.N = K;
-        w.F_in = F_in;
-        w.A = dpb;
-        w.lda = g->ldp;
-        w.Z = Zb;
-        w.ldz = a->ldz;
-        w.R = Rb;
-        w.ldr = a->ld_res;
-        w.gates = g->gates;
-        w.rows_per_split = pl.rows_per_split;
-        w.part_stride = pl.part_stride;
-        w.part = part;
+        const WgradP<uint16_t> w = wgrad_params<uint16_t>(a, g, pl);
         if (bfs) {
             const int tiles = (F_out / WX_BP) * (3 * F_in / WX_BN);
             const unsigned nb = (unsigned)(8 * ((pl.splits + 7) / 8) * tiles);
             hipLaunchKernelGGL(wgrad_bfs_kernel, dim3(nb), dim3(512), 0, s, w, (int)pl.splits);
             if (proj) {  // the residual's columns [3 F_in, 4 F_in): the same partial buffers, no bias sums
-                WgradB wr = w;
+                WgradP<uint16_t> wr = w;
                 wr.col0 = 3 * F_in;
                 dim3 grid((unsigned)((F_in + 127) / 128), (unsigned)((F_out + 127) / 128), (unsigned)pl.splits);
                 hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(512), 0, s, wr);
