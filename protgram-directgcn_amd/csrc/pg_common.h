@@ -88,6 +88,15 @@ inline int check_launch(const char* what) {
     return PG_OK;
 }
 
+// the current device's compute-unit count (256 where the query fails)
+inline int cu_count() {
+    int dev = 0, ncu = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
+        ncu = 256;
+    return ncu;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace pg

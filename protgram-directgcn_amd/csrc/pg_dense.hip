@@ -1342,10 +1342,7 @@ static int dense_launch(const pg_layer_args_t* a, const float* packed, uint32_t 
         ((a->F_in == 128 && !a->W_res) || (a->F_in == 64 && a->W_res))) {
         if (ngmap && a->F_in != 128)
             return pg::set_error(PG_ERR_UNSUPPORTED, "pg_directgcn_dense_ngram_rows_f32: F_in = F_out = 128 only");
-        int dev = 0, ncu = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-            ncu = 256;
+        const int ncu = pg::cu_count();
         if (a->F_in == 128) {  // 16-row software-pipelined kernel
             if (p.rawW && !(pg::aligned16(a->W_main_in) && pg::aligned16(a->W_main_out) &&
                             pg::aligned16(a->W_undirected) && pg::aligned16(a->W_shared)))

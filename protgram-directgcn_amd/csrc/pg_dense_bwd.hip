@@ -904,6 +904,48 @@ struct WgradP {
 constexpr int WROWS = 32;  // rows per K step
 constexpr int WLD = 132;   // LDS row (floats)
 
+// ------------------------------------------------------------------------------------------------
+// Stages shared by the tiled weight-gradient kernels, wgrad_kernel (fp32) and wgrad_bf16_kernel: 128 x 128 output
+// tiles, grid (column tiles, row tiles, row splits). Their stash bodies and bias reductions differ in LDS layout and
+// summation order and stay each kernel's own; so does the one-step double-buffer loop (through a shared template
+// wgrad_kernel<8> took 105 VGPRs instead of 107).
+// ------------------------------------------------------------------------------------------------
+
+// This workgroup's output tile origin (j0: column of B past col0, i0: column of A), its split's rows [r0, rend) and
+// whether it sums the bias gradients (the first column tile of a launch that starts at column 0)
+struct TiledOrigin {
+    int j0, i0;
+    int64_t r0, rend;
+    bool do_db;
+};
+template <typename E>
+__device__ __forceinline__ TiledOrigin tiled_origin(const WgradP<E>& p, int col0) {
+    TiledOrigin o;
+    o.j0 = col0 + blockIdx.x * 128;
+    o.i0 = blockIdx.y * 128;
+    o.r0 = (int64_t)blockIdx.z * p.rows_per_split;
+    o.rend = min(o.r0 + p.rows_per_split, p.M);
+    o.do_db = blockIdx.x == 0 && col0 == 0;
+    return o;
+}
+
+// A wave's 32x32 accumulator tiles into a split's partial `out` [P x N], which may end inside the tile: tile (i, j) at
+// rows oi0 + 32 i, columns oj0 + 32 j (register layout as in acc_park)
+template <int TI, int TJ>
+__device__ __forceinline__ void acc_store_partial(const f32x16 (&acc)[TI][TJ], float* out, int P, int N, int oi0,
+                                                  int oj0, int li, int lh) {
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < TJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int oi = oi0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int oj = oj0 + j * 32 + li;
+                if (oi < P && oj < N) out[(int64_t)oi * N + oj] = acc[i][j][r];
+            }
+}
+
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void wgrad_kernel(WgradP<float> p) {
     constexpr int NT = 64 * NW;
@@ -916,10 +958,10 @@ __global__ __launch_bounds__(64 * NW) void wgrad_kernel(WgradP<float> p) {
     float (*As)[WROWS * WLD] = reinterpret_cast<float (*)[WROWS * WLD]>(smem);
     float (*Bs)[WROWS * WLD] = reinterpret_cast<float (*)[WROWS * WLD]>(smem + 2 * WROWS * WLD);
 
-    const int j0 = blockIdx.x * BJ, i0 = blockIdx.y * BI;
-    const int64_t r0 = (int64_t)blockIdx.z * p.rows_per_split;
-    const int64_t rend = min(r0 + p.rows_per_split, p.M);
-    const bool do_db = blockIdx.x == 0;
+    const TiledOrigin o = tiled_origin(p, 0);
+    const int j0 = o.j0, i0 = o.i0;
+    const int64_t r0 = o.r0, rend = o.rend;
+    const bool do_db = o.do_db;
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int wi = wave / WJ, wj = wave % WJ;
@@ -932,12 +974,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad_kernel(WgradP<float> p) {
     const int64_t ldb = seg < 3 ? p.ldz : p.ldr;
 
     f32x16 acc[TI][TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
     float db[4][4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) db[q][0] = db[q][1] = db[q][2] = db[q][3] = 0.f;
@@ -1013,16 +1050,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad_kernel(WgradP<float> p) {
     }
 
     float* out = p.part + (int64_t)blockIdx.z * p.part_stride;
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < TJ; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int oi = i0 + wi * TI * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                const int oj = j0 + wj * TJ * 32 + j * 32 + li;
-                if (oi < p.P && oj < p.N) out[(int64_t)oi * p.N + oj] = acc[i][j][r];
-            }
+    acc_store_partial(acc, out, p.P, p.N, i0 + wi * TI * 32, j0 + wj * TJ * 32, li, lh);
 
     if (do_db) {  // 16 row groups x 32 column groups x 16 sums -> fixed-order reduction over row groups
         constexpr int RG = NT / 32;
@@ -1070,77 +1098,150 @@ __device__ __forceinline__ void wgrad_tile_of(int b, int tiles, int splits, int&
     if (split >= splits) tile = -1;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Stages shared by the staged weight-gradient kernels, wgrad_x3_kernel (fp32 operands) and wgrad_bfs_kernel (bf16):
+// E the operand element, K the rows per step (WX_K / WB_K), KG = K / 8 its k-groups, CPT the columns per staging
+// thread (8 bytes of a row: 2 floats / 4 bf16). What each kernel keeps as its own copy, and why, is in its comment.
+// ------------------------------------------------------------------------------------------------
+
+// This workgroup's row split, its 128 x 384 output tile (pt, nt) and the split's rows; tile < 0: a split past the last
+// one (the caller returns: its whole workgroup, no barrier reached)
+struct StagedTile {
+    int split, pt, nt;
+    int64_t r0, rend;
+};
+template <typename E>
+__device__ __forceinline__ StagedTile staged_tile(const WgradP<E>& p, int splits, int& tile) {
+    const int n_tiles = min(p.N, 3 * p.F_in) / WX_BN;  // the gated segments (a projected residual's: wgrad_bf16_kernel)
+    StagedTile t;
+    wgrad_tile_of((int)blockIdx.x, (p.P / WX_BP) * n_tiles, splits, t.split, tile);
+    t.pt = tile / n_tiles;
+    t.nt = tile % n_tiles;
+    t.r0 = (int64_t)t.split * p.rows_per_split;
+    t.rend = min(t.r0 + p.rows_per_split, p.M);
+    return t;
+}
+
+// A staging thread (isA: of A = dpre, else of B = Z) with the CPT columns `unit` of one k-group's 8 rows: its image
+// column col0, its segment (3: unscaled, A; gsel: the gate column it loads) and whether it hands the segment's scales
+// to the A threads (the B thread at a segment's first column)
+struct StagedRole {
+    int col0, seg, gsel;
+    bool gwriter;
+};
+template <int CPT>
+__device__ __forceinline__ StagedRole staged_role(int F_in, const StagedTile& t, bool isA, int unit) {
+    StagedRole r;
+    r.col0 = (isA ? 0 : WX_BP) + CPT * unit;
+    const int gcol = isA ? WX_BP * t.pt + CPT * unit : WX_BN * t.nt + CPT * unit;
+    r.seg = isA ? 3 : gcol / F_in;
+    r.gsel = r.seg < 3 ? r.seg : 0;
+    r.gwriter = !isA && gcol % F_in == 0;
+    return r;
+}
+
+// One step's rows of a staging thread (x: 8 bytes of operand bits per row, gq: the rows' scales of its segment)
+// through buffer descriptors over the split's rows: rows past the split read as 0 (the hardware's range check), so the
+// loads and the image stores carry no clamps or selects. xoff / goff: the thread's byte offsets in step 0, ldb: the
+// operand's row pitch in bytes. The offsets are 32-bit: wgrad_staged_offsets_fit (host) keeps the calls they would
+// overflow on off these kernels.
+template <int K>
+__device__ __forceinline__ void staged_load(__amdgpu_buffer_rsrc_t rs_x, __amdgpu_buffer_rsrc_t rs_g, int xoff,
+                                            int goff, int ldb, int step, uint2 (&x)[8], float (&gq)[8]) {
+    const int sx = step * K * ldb, sg = step * K * 16;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+        const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_x, xoff + sx + e * ldb, 0, 0);
+        x[e] = make_uint2(v.x, v.y);
+        gq[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_g, goff + sg + e * 16, 0, 0));
+    }
+}
+
+// The A threads' bias sums db (per k-group, in row order) through Db, summed over the k-groups in k-group order,
+// ((Db[0] + Db[1]) + Db[2]) + Db[3]: a segment's bias belongs to the n-tile holding its first column, the unscaled one
+// (q = 3) to n-tile 0.
+template <int KG, int CPT, typename E>
+__device__ __forceinline__ void staged_bias_reduce(const WgradP<E>& p, const StagedTile& tl, float (&Db)[KG][4][WX_BP],
+                                                   const float (&db)[4][CPT], bool isA, int kg, int unit, int tid,
+                                                   float* out) {
+    if (isA) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) Db[kg][t][CPT * unit + c] = db[t][c];
+    }
+    __syncthreads();
+    const int t = tid >> 7, c = tid & 127;  // 4 x 128 sums
+    const int first = t * p.F_in;            // the segment's first column
+    const bool mine = t == 3 ? tl.nt == 0 : (first >= WX_BN * tl.nt && first < WX_BN * (tl.nt + 1));
+    if (mine) {
+        float v = Db[0][t][c];
+#pragma unroll
+        for (int g = 1; g < KG; ++g) v += Db[g][t][c];
+        out[(int64_t)p.P * p.N + t * p.P + WX_BP * tl.pt + c] = v;
+    }
+}
+
+// wgrad_x3_kernel (header above the shared stages). Its own copies: the two-steps-ahead loop (as a shared template it
+// is equal here but took 232 VGPRs instead of 240 in wgrad_bfs_kernel), the descriptors (a shared struct holding them
+// took 255 VGPRs here), the accumulator store (through a shared template +100 instructions in both kernels) and what
+// differs by design: role mapping, split_store, bias_step, mfma_step.
 __global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgradP<float> p, int splits) {
     __shared__ __attribute__((aligned(16))) uint4 U[2][3][2][WX_COLS];
     __shared__ float Db[2][4][WX_BP];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, kh = lane >> 5;
-    const int n_tiles = min(p.N, 3 * p.F_in) / WX_BN;  // the gated segments (a projected residual's: wgrad_bf16_kernel)
-    int split, tile;
-    wgrad_tile_of((int)blockIdx.x, (p.P / WX_BP) * n_tiles, splits, split, tile);
+    int tile;
+    const StagedTile tl = staged_tile(p, splits, tile);
     if (tile < 0) return;  // whole workgroup: no barrier reached
-    const int pt = tile / n_tiles, nt = tile % n_tiles;
-    const int64_t r0 = (int64_t)split * p.rows_per_split;
-    const int64_t rend = min(r0 + p.rows_per_split, p.M);
     // staging role, from the wave index in a scalar register (so the buffer descriptors below are wave-uniform):
     // waves 0-1 stage A (k-group = wave), waves 2-4 / 5-7 B (k-group 0 / 1), 64 column pairs per wave
     const int wv = __builtin_amdgcn_readfirstlane(wave);
     const bool isA = wv < 2;
     const int kg = isA ? wv : (wv - 2) / 3;
     const int pair = (isA ? 0 : 64 * ((wv - 2) % 3)) + lane;
-    const int col0 = (isA ? 0 : WX_BP) + 2 * pair;              // staged column (image index)
-    const int gcol = isA ? WX_BP * pt + 2 * pair : WX_BN * nt + 2 * pair;
-    const int seg = isA ? 3 : gcol / p.F_in;  // 3: unscaled (A)
-    const float* src = isA ? p.A + WX_BP * pt : p.Z + WX_BN * nt;  // wave-uniform; the lane's columns: + 2 pair
+    const StagedRole rl = staged_role<2>(p.F_in, tl, isA, pair);
+    const float* src = isA ? p.A + WX_BP * tl.pt : p.Z + WX_BN * tl.nt;  // wave-uniform; the lane's columns: + 2 pair
     const int64_t ld = isA ? p.lda : p.ldz;
-    // Two register slots of one step's rows each (x: the operand values, gq: the row's scale of this thread's segment),
-    // loaded two steps ahead through buffer descriptors over the split's rows: rows past the split read as 0 (the
-    // hardware's range check), so the loads and splits carry no clamps or selects. The bias sums need the three
-    // gates of every row in the A threads: the B thread at the first column of a segment writes its scales to Gs with
-    // the images, and the A threads add the step's sums after the barrier, from the split-time values they keep (va,
-    // vb). A segment's bias belongs to the n-tile holding its first column, the unscaled one (q = 3) to n-tile 0.
-    __shared__ float Gs[2][3][WX_K];
-    const int gsel = seg < 3 ? seg : 0;
-    const bool gwriter = !isA && gcol % p.F_in == 0;
-    const int64_t nr64 = rend - r0;
+    // Two register slots of one step's rows each, loaded two steps ahead (staged_load)
+    const int64_t nr64 = tl.rend - tl.r0;
     const int nrows = __builtin_amdgcn_readfirstlane(nr64 > 0 ? (int)nr64 : 0);  // scalar (descriptor word 2)
-    const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src + r0 * ld), 0, nrows * (int)ld * 4,
+    const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src + tl.r0 * ld), 0, nrows * (int)ld * 4,
                                                         0x00020000);
-    const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gates + r0 * 4), 0, nrows * 16, 0x00020000);
+    const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gates + tl.r0 * 4), 0, nrows * 16,
+                                                        0x00020000);
     const int ld4b = (int)ld * 4;
-    const int xoff = 8 * kg * ld4b + 8 * pair, goff = (8 * kg * 4 + gsel) * 4;
-    auto load = [&](float2 (&x)[8], float (&gq)[8], int step) {  // step < 2^31 / (16 ld) (host-checked)
-        const int sx = step * WX_K * ld4b, sg = step * WX_K * 16;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_x, xoff + sx + e * ld4b, 0, 0);
-            x[e] = make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
-            gq[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_g, goff + sg + e * 16, 0, 0));
-        }
+    const int xoff = 8 * kg * ld4b + 8 * pair, goff = (8 * kg * 4 + rl.gsel) * 4;
+    auto load = [&](uint2 (&x)[8], float (&gq)[8], int step) {
+        staged_load<WX_K>(rs_x, rs_g, xoff, goff, ld4b, step, x, gq);
     };
+    // The bias sums need the three gates of every row in the A threads: the B thread at the first column of a segment
+    // writes its scales to Gs with the images, and the A threads add the step's sums after the barrier, from the
+    // split-time values they keep (va, vb).
+    __shared__ float Gs[2][3][WX_K];
     float db[4][2];
 #pragma unroll
     for (int t = 0; t < 4; ++t) db[t][0] = db[t][1] = 0.f;
     float va[8], vb[8];
-    auto split_store = [&](const float2 (&x)[8], const float (&gq)[8], int buf) {
+    auto split_store = [&](const uint2 (&x)[8], const float (&gq)[8], int buf) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float sc = isA ? 1.f : gq[e];
-            va[e] = __fmul_rn(x[e].x, sc);
-            vb[e] = __fmul_rn(x[e].y, sc);
+            va[e] = __fmul_rn(__uint_as_float(x[e].x), sc);
+            vb[e] = __fmul_rn(__uint_as_float(x[e].y), sc);
         }
         uint4 a0, a1, a2, b0, b1, b2;
         pgx3::split8(va, a0, a1, a2);
         pgx3::split8(vb, b0, b1, b2);
-        U[buf][0][kg][col0] = a0;
-        U[buf][1][kg][col0] = a1;
-        U[buf][2][kg][col0] = a2;
-        U[buf][0][kg][col0 + 1] = b0;
-        U[buf][1][kg][col0 + 1] = b1;
-        U[buf][2][kg][col0 + 1] = b2;
-        if (gwriter) {
+        U[buf][0][kg][rl.col0] = a0;
+        U[buf][1][kg][rl.col0] = a1;
+        U[buf][2][kg][rl.col0] = a2;
+        U[buf][0][kg][rl.col0 + 1] = b0;
+        U[buf][1][kg][rl.col0 + 1] = b1;
+        U[buf][2][kg][rl.col0 + 1] = b2;
+        if (rl.gwriter) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) Gs[buf][seg][8 * kg + e] = gq[e];
+            for (int e = 0; e < 8; ++e) Gs[buf][rl.seg][8 * kg + e] = gq[e];
         }
     };
     auto bias_step = [&](int cur) {  // A threads, after the barrier: the step's rows' bias sums, in row order
@@ -1158,12 +1259,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgradP<float> p, int s
     };
     if (tid < 2 * 3 * WX_K) (&Gs[0][0][0])[tid] = 0.f;  // segments that start in another n-tile stay 0
     f32x16 acc[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
     const int ih = wave & 1, jq = wave >> 1;
     auto mfma_step = [&](int cur) {
         uint4 a[2][3];
@@ -1189,9 +1285,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgradP<float> p, int s
     };
     // step t: slot t & 1 takes step t + 2's rows, the MFMAs read image t & 1, slot (t + 1) & 1 (step t + 1's rows,
     // loaded a step ago) is split into image (t + 1) & 1; one barrier
-    float2 x0[8], x1[8];
+    uint2 x0[8], x1[8];
     float g0[8], g1[8];
-    const int64_t nsteps = (rend - r0 + WX_K - 1) / WX_K;
+    const int64_t nsteps = (tl.rend - tl.r0 + WX_K - 1) / WX_K;
     __syncthreads();  // Gs zeroed
     // Loads and splits are unconditional (past the last step: clamped rows, zero images, zero bias terms): VMEM
     // loads under a branch would make the compiler's wait counts assume the worst at the join -- waiting for the
@@ -1212,31 +1308,18 @@ __global__ __launch_bounds__(512, 1) void wgrad_x3_kernel(WgradP<float> p, int s
         split_store(x0, g0, 0);
         __syncthreads();
     }
-    float* out = p.part + (int64_t)split * p.part_stride;
+    float* out = p.part + (int64_t)tl.split * p.part_stride;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int oi = WX_BP * pt + 64 * ih + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                const int oj = WX_BN * nt + 96 * jq + 32 * j + li;
+                const int oi = WX_BP * tl.pt + 64 * ih + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int oj = WX_BN * tl.nt + 96 * jq + 32 * j + li;
                 out[(int64_t)oi * p.N + oj] = acc[i][j][r];
             }
-    if (isA) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            Db[kg][t][2 * pair] = db[t][0];
-            Db[kg][t][2 * pair + 1] = db[t][1];
-        }
-    }
-    __syncthreads();
-    {
-        const int t = tid >> 7, c = tid & 127;  // 4 x 128 sums, k-groups in fixed order
-        const int first = t * p.F_in;            // the segment's first column (q = 3: n-tile 0)
-        const bool mine = t == 3 ? nt == 0 : (first >= WX_BN * nt && first < WX_BN * (nt + 1));
-        if (mine) out[(int64_t)p.P * p.N + t * p.P + WX_BP * pt + c] = Db[0][t][c] + Db[1][t][c];
-    }
+    staged_bias_reduce(p, tl, Db, db, isA, kg, pair, tid, out);
 }
 
 // out[c] = sum_s part[s][c]. A block owns 32 consecutive float4 columns (512 contiguous bytes per split);
@@ -1777,10 +1860,10 @@ __global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradP<uint16_t> p) 
     constexpr int BI = 128, BJ = 128;
     __shared__ __attribute__((aligned(16))) uint16_t At[2][BI * LDM];
     __shared__ __attribute__((aligned(16))) uint16_t Bt[2][BJ * LDM];
-    const int j0 = p.col0 + blockIdx.x * BJ, i0 = blockIdx.y * BI;
-    const int64_t r0 = (int64_t)blockIdx.z * p.rows_per_split;
-    const int64_t rend = min(r0 + p.rows_per_split, p.M);
-    const bool do_db = blockIdx.x == 0 && p.col0 == 0;
+    const TiledOrigin o = tiled_origin(p, p.col0);
+    const int j0 = o.j0, i0 = o.i0;
+    const int64_t r0 = o.r0, rend = o.rend;
+    const bool do_db = o.do_db;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wi = wave >> 1, wj = wave & 1;  // wave tile 32 (i) x 64 (j)
     const int li = lane & 31, lh = lane >> 5;
@@ -1793,11 +1876,8 @@ __global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradP<uint16_t> p) 
     const int64_t ld = half ? (seg < 3 ? p.ldz : p.ldr) : p.lda;
     const bool need_s = half || do_db;
 
-    f32x16 acc[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    f32x16 acc[1][2];
+    acc_zero(acc);
     float db[4][8];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -1870,7 +1950,7 @@ __global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradP<uint16_t> p) 
             for (int j = 0; j < 2; ++j) {
                 const bf16x8 b = __builtin_bit_cast(
                     bf16x8, *reinterpret_cast<const uint4*>(&Bt[cur][(wj * 64 + j * 32 + li) * LDM + ks * 16 + 8 * lh]));
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
+                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[0][j], 0, 0, 0);
             }
         }
         if (t + 1 < nsteps) stash(cur ^ 1, nb);
@@ -1878,14 +1958,7 @@ __global__ __launch_bounds__(512, 4) void wgrad_bf16_kernel(WgradP<uint16_t> p) 
     }
 
     float* out = p.part + (int64_t)blockIdx.z * p.part_stride;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int oi = i0 + wi * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const int oj = j0 + wj * 64 + j * 32 + li;
-            if (oi < p.P && oj < p.N) out[(int64_t)oi * p.N + oj] = acc[j][r];
-        }
+    acc_store_partial(acc, out, p.P, p.N, i0 + wi * 32, j0 + wj * 64, li, lh);
     if (do_db && !half) {  // sum the 16 row pairs of each column group (16 consecutive lanes)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -1945,6 +2018,9 @@ SplitPlan split_rows(int64_t M, int64_t tiles) {
 // one XCD at neighbouring times (blockIdx -> (split, tile), see wgrad_tile_of), so the tiles that read the same rows
 // share them through that XCD's L2. wgrad_bf16_kernel (128 x 128 tiles, one step of prefetch) re-read dpre once per
 // 128-column tile: 984 MB at F = 256 against the 656 MB here.
+// Shares wgrad_x3_kernel's stages (staged_tile, staged_role, staged_load, acc_zero, staged_bias_reduce) and keeps the
+// same stages as its own copies, for the reasons given there: moved into any inlined function, even verbatim, the
+// two-steps-ahead loop compiles to 232 VGPRs here instead of 240.
 constexpr int WB_K = 32;  // rows per step (4 k-groups of 8)
 
 __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, int splits) {
@@ -1952,13 +2028,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, i
     __shared__ float Db[4][4][WX_BP];
     __shared__ float Gs[2][3][WB_K];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, kh = lane >> 5;
-    const int n_tiles = p.N / WX_BN;
-    int split, tile;
-    wgrad_tile_of((int)blockIdx.x, (p.P / WX_BP) * n_tiles, splits, split, tile);
+    int tile;
+    const StagedTile tl = staged_tile(p, splits, tile);
     if (tile < 0) return;  // whole workgroup: no barrier reached
-    const int pt = tile / n_tiles, nt = tile % n_tiles;
-    const int64_t r0 = (int64_t)split * p.rows_per_split;
-    const int64_t rend = min(r0 + p.rows_per_split, p.M);
     // staging role: waves 0-1 stage A (128 columns: 32 quads x 4 k-groups), waves 2-7 B (384 columns: 96 x 4); the
     // wave index in a scalar register keeps the buffer descriptors wave-uniform
     const int wv = __builtin_amdgcn_readfirstlane(wave);
@@ -1966,29 +2038,19 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, i
     const int u = isA ? tid : tid - 128;
     const int kg = isA ? (u >> 5) : (u / 96);
     const int quad = isA ? (u & 31) : (u % 96);
-    const int col0 = (isA ? 0 : WX_BP) + 4 * quad;
-    const int gcol = isA ? WX_BP * pt + 4 * quad : WX_BN * nt + 4 * quad;
-    const int seg = isA ? 3 : gcol / p.F_in;
-    const uint16_t* src = isA ? p.A + WX_BP * pt : p.Z + WX_BN * nt;
+    const StagedRole rl = staged_role<4>(p.F_in, tl, isA, quad);
+    const uint16_t* src = isA ? p.A + WX_BP * tl.pt : p.Z + WX_BN * tl.nt;
     const int64_t ld = isA ? p.lda : p.ldz;
-    const int gsel = seg < 3 ? seg : 0;
-    const bool gwriter = !isA && gcol % p.F_in == 0;
-    const int64_t nr64 = rend - r0;
+    const int64_t nr64 = tl.rend - tl.r0;
     const int nrows = __builtin_amdgcn_readfirstlane(nr64 > 0 ? (int)nr64 : 0);
-    const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(src + r0 * ld), 0, nrows * (int)ld * 2,
+    const auto rs_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(src + tl.r0 * ld), 0, nrows * (int)ld * 2,
                                                         0x00020000);
-    const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gates + r0 * 4), 0, nrows * 16, 0x00020000);
+    const auto rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gates + tl.r0 * 4), 0, nrows * 16,
+                                                        0x00020000);
     const int ld2b = (int)ld * 2;
-    const int xoff = 8 * kg * ld2b + 8 * quad, goff = (8 * kg * 4 + gsel) * 4;
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    auto load = [&](uint2 (&x)[8], float (&gq)[8], int step) {  // step < 2^31 / (32 ld) (host-checked)
-        const int sx = step * WB_K * ld2b, sg = step * WB_K * 16;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs_x, xoff + sx + e * ld2b, 0, 0);
-            x[e] = make_uint2(v.x, v.y);
-            gq[e] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs_g, goff + sg + e * 16, 0, 0));
-        }
+    const int xoff = 8 * kg * ld2b + 8 * quad, goff = (8 * kg * 4 + rl.gsel) * 4;
+    auto load = [&](uint2 (&x)[8], float (&gq)[8], int step) {
+        staged_load<WB_K>(rs_x, rs_g, xoff, goff, ld2b, step, x, gq);
     };
     float db[4][4];
 #pragma unroll
@@ -2026,10 +2088,10 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, i
             }
         }
 #pragma unroll
-        for (int c = 0; c < 4; ++c) U[buf][kg][col0 + c] = make_uint4(w[c][0], w[c][1], w[c][2], w[c][3]);
-        if (gwriter) {
+        for (int c = 0; c < 4; ++c) U[buf][kg][rl.col0 + c] = make_uint4(w[c][0], w[c][1], w[c][2], w[c][3]);
+        if (rl.gwriter) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) Gs[buf][seg][8 * kg + e] = gq[e];
+            for (int e = 0; e < 8; ++e) Gs[buf][rl.seg][8 * kg + e] = gq[e];
         }
     };
     auto bias_step = [&](int cur) {  // A threads, after the barrier: the step's rows in order
@@ -2047,12 +2109,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, i
     };
     if (tid < 2 * 3 * WB_K) (&Gs[0][0][0])[tid] = 0.f;
     f32x16 acc[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_zero(acc);
     const int ih = wave & 1, jq = wave >> 1;
     auto mfma_step = [&](int cur) {
 #pragma unroll
@@ -2071,9 +2128,9 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, i
     };
     uint2 x0[8], x1[8];
     float g0[8], g1[8];
-    const int64_t nsteps = (rend - r0 + WB_K - 1) / WB_K;
+    const int64_t nsteps = (tl.rend - tl.r0 + WB_K - 1) / WB_K;
     __syncthreads();  // Gs zeroed
-    // loads and packs unconditional (past the last step: zero rows), as in wgrad_x3_kernel
+    // the two-steps-ahead pipeline of wgrad_x3_kernel; loads and packs unconditional (past the last step: zero rows)
     load(x0, g0, 0);
     load(x1, g1, 1);
     pack_store(x0, g0, 0);
@@ -2090,30 +2147,18 @@ __global__ __launch_bounds__(512, 1) void wgrad_bfs_kernel(WgradP<uint16_t> p, i
         pack_store(x0, g0, 0);
         __syncthreads();
     }
-    float* out = p.part + (int64_t)split * p.part_stride;
+    float* out = p.part + (int64_t)tl.split * p.part_stride;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int oi = WX_BP * pt + 64 * ih + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                const int oj = WX_BN * nt + 96 * jq + 32 * j + li;
+                const int oi = WX_BP * tl.pt + 64 * ih + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                const int oj = WX_BN * tl.nt + 96 * jq + 32 * j + li;
                 out[(int64_t)oi * p.N + oj] = acc[i][j][r];
             }
-    if (isA) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) Db[kg][t][4 * quad + c] = db[t][c];
-    }
-    __syncthreads();
-    {
-        const int t = tid >> 7, c = tid & 127;  // 4 x 128 sums, k-groups in fixed order
-        const int first = t * p.F_in;
-        const bool mine = t == 3 ? nt == 0 : (first >= WX_BN * nt && first < WX_BN * (nt + 1));
-        if (mine) out[(int64_t)p.P * p.N + t * p.P + WX_BP * pt + c] = ((Db[0][t][c] + Db[1][t][c]) + Db[2][t][c]) + Db[3][t][c];
-    }
+    staged_bias_reduce(p, tl, Db, db, isA, kg, quad, tid, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2177,39 +2222,31 @@ __global__ __launch_bounds__(256) void dgrad_generic_kernel(DgradP<float> p) {
 
 // partial [split][F_out * K + 4 F_out]: dB[o][j] = sum_m s_seg(j)[m] dpre[m][o] A[m][j] (A = Z, or res_x in
 // segment 3 with s = 1), dbsum[q][o] = sum_m s_q[m] dpre[m][o] (q = 3: the projected residual's bias, else 0)
-struct WgradGenP {
-    int64_t M;
-    int F_in, F_out, K, proj;
-    const float *dpre, *Z, *R, *gates;
-    int64_t ldp, ldz, ldr;
-    int64_t rows_per_split, part_stride;
-    float* part;
-};
-
-__global__ __launch_bounds__(256) void wgrad_generic_kernel(WgradGenP w) {
+// (WgradP<float>: P = F_out, N = K, A = dpre)
+__global__ __launch_bounds__(256) void wgrad_generic_kernel(WgradP<float> w) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t n = (int64_t)w.F_out * (w.K + 4);
+    const int64_t n = (int64_t)w.P * (w.N + 4);
     if (idx >= n) return;
     const int64_t m0 = (int64_t)blockIdx.y * w.rows_per_split;
     const int64_t m1 = m0 + w.rows_per_split < w.M ? m0 + w.rows_per_split : w.M;
     float acc = 0.f;
     int64_t out;
-    if (idx < (int64_t)w.F_out * w.K) {  // dB[o][j], j fastest
-        const int o = (int)(idx / w.K), j = (int)(idx % w.K);
+    if (idx < (int64_t)w.P * w.N) {  // dB[o][j], j fastest
+        const int o = (int)(idx / w.N), j = (int)(idx % w.N);
         const int seg = j / w.F_in;
         for (int64_t m = m0; m < m1; ++m) {
             const float a = seg < 3 ? w.Z[m * w.ldz + j] : w.R[m * w.ldr + (j - 3 * w.F_in)];
             const float sv = seg < 3 ? w.gates[m * 4 + seg] : 1.f;
-            acc += sv * w.dpre[m * w.ldp + o] * a;
+            acc += sv * w.A[m * w.lda + o] * a;
         }
         out = idx;
     } else {
-        const int64_t t = idx - (int64_t)w.F_out * w.K;
-        const int q = (int)(t / w.F_out), o = (int)(t % w.F_out);
+        const int64_t t = idx - (int64_t)w.P * w.N;
+        const int q = (int)(t / w.P), o = (int)(t % w.P);
         // row 3 = the column sums of dpre with or without a projected residual, as the MFMA kernels give it (their
         // fourth gate column is 1): the same dW whichever kernels a layout selects
-        for (int64_t m = m0; m < m1; ++m) acc += (q < 3 ? w.gates[m * 4 + q] : 1.f) * w.dpre[m * w.ldp + o];
-        out = (int64_t)w.F_out * w.K + (int64_t)q * w.F_out + o;
+        for (int64_t m = m0; m < m1; ++m) acc += (q < 3 ? w.gates[m * 4 + q] : 1.f) * w.A[m * w.lda + o];
+        out = (int64_t)w.P * w.N + (int64_t)q * w.P + o;
     }
     w.part[(int64_t)blockIdx.y * w.part_stride + out] = acc;
 }
@@ -2228,6 +2265,22 @@ int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
 // the split-bf16 weight gradient (wgrad_x3_kernel: 128 x 384 output tiles) takes these shapes
 bool wgrad_x3_shape(int64_t F_in, int64_t F_out, bool proj) {
     return F_in % (WX_BN / 3) == 0 && F_out % WX_BP == 0 && !proj;
+}
+
+// Do the staged kernels' 32-bit byte offsets fit for this call? K: rows per step (WX_K / WB_K), eb: bytes per
+// operand element, rows_per_split: the staged plan's. staged_load forms, for an operand of leading dimension ld,
+//   xoff + sx + e ldb = ((8 kg + e) + step K) ld eb + 8 unit,
+// relative to the split's first row (the descriptor's base, a 64-bit address). With n = ceil(rows_per_split / K) steps
+// the loop's last trip is t = n - 1 (n odd) or n - 2 (n even) and prefetches steps t + 2 and t + 3, so step <= n + 2;
+// 8 kg + e <= K - 1; 8 unit + 8 <= WX_BN eb (the lane's columns and its 8-byte load). So every offset, every product
+// inside it and the descriptor's size nrows ld eb (nrows <= rows_per_split) stay below
+//   (n + 3) K ld eb + WX_BN eb,
+// which must not exceed 2^31 - 1 for both operands (dpre with ldp, Z with ldz); the gates' offsets likewise below
+// (n + 3) K 16 + 16. Where this fails the tiled kernels run: they index rows with 64-bit offsets.
+bool wgrad_staged_offsets_fit(int64_t rows_per_split, int K, int64_t eb, int64_t ldp, int64_t ldz) {
+    const int64_t rows = ((rows_per_split + K - 1) / K + 3) * K, lim = INT32_MAX;
+    const int64_t ld = std::max(ldp, ldz);
+    return rows * 16 + 16 <= lim && ld <= lim / (rows * eb) && rows * ld * eb + WX_BN * eb <= lim;
 }
 
 // x3w: the row splits of wgrad_x3_kernel (one 512-thread workgroup per CU over all output tiles, 16-row steps)
@@ -2350,6 +2403,66 @@ WgradP<E> wgrad_params(const pg_layer_args_t* a, const pg_layer_grad_args_t* g, 
     w.part = g->work + pl.off_part;
     return w;
 }
+// the plain C = A^T B (pg_gemm_at_b_f32): one segment, null gates (unit scales), no residual
+WgradP<float> wgrad_params(int64_t M, int64_t P, int64_t N, const float* A, int64_t lda, const float* B, int64_t ldb,
+                           const SplitPlan& sp, int64_t part_stride, float* part) {
+    WgradP<float> w{};
+    w.M = M;
+    w.P = (int)P;
+    w.N = (int)N;
+    w.F_in = (int)N;
+    w.A = A;
+    w.lda = lda;
+    w.Z = B;
+    w.ldz = ldb;
+    w.rows_per_split = sp.rows_per_split;
+    w.part_stride = part_stride;
+    w.part = part;
+    return w;
+}
+
+// The staged plan where the shape takes the staged kernels (shape_ok: wgrad_x3_shape and the entry point's own
+// conditions) and their 32-bit offsets fit (wgrad_staged_offsets_fit), else the tiled plan; staged says which
+BwdPlan wgrad_plan(const pg_layer_args_t* a, const pg_layer_grad_args_t* g, bool shape_ok, int K, int64_t eb,
+                   bool& staged) {
+    const bool proj = a->W_res != nullptr;
+    staged = shape_ok;
+    if (staged) {
+        const BwdPlan pl = plan_of(a->M, a->F_in, a->F_out, proj, true);
+        if (wgrad_staged_offsets_fit(pl.rows_per_split, K, eb, g->ldp, a->ldz)) return pl;
+        staged = false;
+    }
+    return plan_of(a->M, a->F_in, a->F_out, proj, false);
+}
+
+void launch_gate_grad(int64_t M, int ntn, const float* dsp, const Gates& gt, float* dgate, hipStream_t s) {
+    const int nb = (int)std::min<int64_t>((M + 255) / 256, 2048);
+    hipLaunchKernelGGL(gate_grad_kernel, dim3(nb), dim3(256), 0, s, M, ntn, dsp, gt, dgate);
+}
+
+// The weight gradient's partials: the staged kernel over the gated segments' 128 x 384 tiles (then, bf16 with a
+// projected residual, its proj_cols columns [3 F_in, N) on the tiled kernel beside it: the same partial buffers, no
+// bias sums), else the tiled kernel over all columns
+template <typename E>
+void launch_wgrad(const WgradP<E>& w, int splits, bool staged, int proj_cols, hipStream_t s) {
+    constexpr bool f32 = std::is_same<E, float>::value;
+    const unsigned pt128 = (unsigned)((w.P + 127) / 128);
+    auto tiled = [&](const WgradP<E>& wt, int cols) {
+        const dim3 grid((unsigned)((cols + 127) / 128), pt128, (unsigned)splits);
+        if constexpr (f32) hipLaunchKernelGGL((wgrad_kernel<WG_NW>), grid, dim3(64 * WG_NW), 0, s, wt);
+        else hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(512), 0, s, wt);
+    };
+    if (!staged) return tiled(w, w.N);
+    const int tiles = (w.P / WX_BP) * (3 * w.F_in / WX_BN);
+    const dim3 grid((unsigned)(8 * ((splits + 7) / 8) * tiles));
+    if constexpr (f32) hipLaunchKernelGGL(wgrad_x3_kernel, grid, dim3(512), 0, s, w, splits);
+    else hipLaunchKernelGGL(wgrad_bfs_kernel, grid, dim3(512), 0, s, w, splits);
+    if (proj_cols) {
+        WgradP<E> wr = w;
+        wr.col0 = 3 * w.F_in;
+        tiled(wr, proj_cols);
+    }
+}
 
 // the fp32 backward; span != nullptr: pg_directgcn_dense_bwd_span_f32 (dgrad_span_kernel, E = diagonal term of the
 // transposed propagation (+ residual), PG_ERR_UNSUPPORTED unless its shape conditions hold)
@@ -2358,8 +2471,9 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
     float drop_s = 0.f;
     if (const int rc = bwd_check_args(a, packed != nullptr, g, drop_s)) return rc;
     const bool proj = a->W_res != nullptr;
-    const bool x3w = wgrad_x3_shape(a->F_in, a->F_out, proj) && !(flags & PG_FLAG_WGRAD_F32MFMA);
-    const BwdPlan pl = plan_of(a->M, a->F_in, a->F_out, proj, x3w);
+    bool x3w;
+    const BwdPlan pl = wgrad_plan(a, g, wgrad_x3_shape(a->F_in, a->F_out, proj) && !(flags & PG_FLAG_WGRAD_F32MFMA),
+                                  WX_K, sizeof(float), x3w);
     PG_REQUIRE(g->work_floats >= pl.total, "workspace too small: %lld < %lld floats", (long long)g->work_floats,
                (long long)pl.total);
     // vector paths only: every row / column block is float4
@@ -2376,7 +2490,7 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
                GEN_MAX_FOUT);
     hipStream_t s = (hipStream_t)stream;
     const int K = pl.K;
-    const int F_in = (int)a->F_in, F_out = (int)a->F_out;
+    const int F_out = (int)a->F_out;
     float* BT = g->work + pl.off_bt;
     float* dsp = g->work + pl.off_dsp;
     float* part = g->work + pl.off_part;
@@ -2399,27 +2513,10 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
     if (!vec) {  // any shape: per-element kernels (same outputs, sums in another order)
         const unsigned nb = (unsigned)std::min<int64_t>(a->M, 8192);
         hipLaunchKernelGGL(dgrad_generic_kernel, dim3(nb), dim3(256), 0, s, p);
-        const int gb = (int)std::min<int64_t>((a->M + 255) / 256, 2048);
-        hipLaunchKernelGGL(gate_grad_kernel, dim3(gb), dim3(256), 0, s, a->M, 1, (const float*)dsp, gt, g->dgate);
-        WgradGenP w{};
-        w.M = a->M;
-        w.F_in = F_in;
-        w.F_out = F_out;
-        w.K = K;
-        w.proj = proj ? 1 : 0;
-        w.dpre = g->dpre;
-        w.ldp = g->ldp;
-        w.Z = a->Z;
-        w.ldz = a->ldz;
-        w.R = a->res_x;
-        w.ldr = a->ld_res;
-        w.gates = g->gates;
-        w.rows_per_split = pl.rows_per_split;
-        w.part_stride = pl.part_stride;
-        w.part = part;
+        launch_gate_grad(a->M, 1, dsp, gt, g->dgate, s);
         const int64_t n = (int64_t)F_out * (K + 4);
         hipLaunchKernelGGL(wgrad_generic_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)pl.splits), dim3(256), 0, s,
-                           w);
+                           wgrad_params<float>(a, g, pl));
         hipLaunchKernelGGL(reduce_generic_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, pl.splits,
                            pl.part_stride, (const float*)part, g->dW);
         return pg::check_launch("pg_directgcn_dense_bwd_f32");
@@ -2435,22 +2532,8 @@ int dense_bwd_f32_impl(const pg_layer_args_t* a, const float* packed, const pg_l
                                dim3(64 * X3_NW), 0, s, p, (const uint16_t*)BT3);
         else hipLaunchKernelGGL((dgrad_kernel<DG_BM, DG_BN, DG_NW>), dim3((unsigned)nb), dim3(64 * DG_NW), 0, s, p);
     }
-    {
-        const int nb = (int)std::min<int64_t>((a->M + 255) / 256, 2048);
-        hipLaunchKernelGGL(gate_grad_kernel, dim3(nb), dim3(256), 0, s, a->M, span ? (int)(a->F_in / 64) : pl.ntn,
-                           (const float*)dsp, gt, g->dgate);
-    }
-    {
-        const WgradP<float> w = wgrad_params<float>(a, g, pl);
-        if (x3w) {
-            const int tiles = (F_out / WX_BP) * (K / WX_BN);
-            hipLaunchKernelGGL(wgrad_x3_kernel, dim3((unsigned)(8 * ((pl.splits + 7) / 8) * tiles)), dim3(512), 0, s, w,
-                               (int)pl.splits);
-        } else {
-            dim3 grid((unsigned)((K + 127) / 128), (unsigned)((F_out + 127) / 128), (unsigned)pl.splits);
-            hipLaunchKernelGGL((wgrad_kernel<WG_NW>), grid, dim3(64 * WG_NW), 0, s, w);
-        }
-    }
+    launch_gate_grad(a->M, span ? (int)(a->F_in / 64) : pl.ntn, dsp, gt, g->dgate, s);
+    launch_wgrad(wgrad_params<float>(a, g, pl), pl.splits, x3w, 0, s);
     // F_out % 4 == 0, so part_stride == F_out*K + 4*F_out == the dW buffer
     launch_reduce(pl.part_stride / 4, pl.splits, pl.part_stride, part, g->dW, s);
     return pg::check_launch(span ? "pg_directgcn_dense_bwd_span_f32" : "pg_directgcn_dense_bwd_f32");
@@ -2512,23 +2595,7 @@ int pg_gemm_at_b_f32(int64_t M, int64_t P, int64_t N, const float* A, int64_t ld
     const int64_t stride = up4(P * N + 4 * P);
     PG_REQUIRE(work_floats >= (int64_t)sp.splits * stride, "workspace too small: %lld < %lld floats",
                (long long)work_floats, (long long)sp.splits * stride);
-    WgradP<float> w{};
-    w.M = M;
-    w.P = (int)P;
-    w.N = (int)N;
-    w.F_in = (int)N;  // one segment, unit scales
-    w.A = A;
-    w.lda = lda;
-    w.Z = B;
-    w.ldz = ldb;
-    w.R = nullptr;
-    w.ldr = 0;
-    w.gates = nullptr;
-    w.rows_per_split = sp.rows_per_split;
-    w.part_stride = stride;
-    w.part = work;
-    dim3 grid((unsigned)((N + 127) / 128), (unsigned)((P + 127) / 128), (unsigned)sp.splits);
-    hipLaunchKernelGGL((wgrad_kernel<WG_NW>), grid, dim3(64 * WG_NW), 0, s, w);
+    launch_wgrad(wgrad_params(M, P, N, A, lda, B, ldb, sp, stride, work), sp.splits, false, 0, s);
     launch_reduce((P * N + P) / 4, sp.splits, stride, work, out, s);  // C, then colsum(A) (db row 0)
     return pg::check_launch("pg_gemm_at_b_f32");
 }
@@ -2541,10 +2608,13 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
     // the staged weight gradient (wgrad_bfs_kernel) where its tiles fit; PG_FLAG_WGRAD_BF16_TILED keeps the 128 x 128
     // tiles of wgrad_bf16_kernel
     // (with a projected residual, its F_in columns then run on wgrad_bf16_kernel beside it)
-    const bool bfs = wgrad_x3_shape(a->F_in, a->F_out, false) && !(flags & PG_FLAG_WGRAD_BF16_TILED) &&
-                     a->ldz % 4 == 0 && g->ldp % 4 == 0 && (reinterpret_cast<uintptr_t>(a->Z) & 7) == 0 &&
-                     (reinterpret_cast<uintptr_t>(g->dpre) & 7) == 0;
-    const BwdPlan pl = plan_of(a->M, a->F_in, a->F_out, proj, bfs);
+    bool bfs;
+    const BwdPlan pl = wgrad_plan(a, g,
+                                  wgrad_x3_shape(a->F_in, a->F_out, false) && !(flags & PG_FLAG_WGRAD_BF16_TILED) &&
+                                      a->ldz % 4 == 0 && g->ldp % 4 == 0 &&
+                                      (reinterpret_cast<uintptr_t>(a->Z) & 7) == 0 &&
+                                      (reinterpret_cast<uintptr_t>(g->dpre) & 7) == 0,
+                                  WB_K, sizeof(uint16_t), bfs);
     PG_REQUIRE(g->work_floats >= pl.total, "workspace too small");
     const uint16_t* Zb = reinterpret_cast<const uint16_t*>(a->Z);
     const uint16_t* Yb = reinterpret_cast<const uint16_t*>(a->Y);
@@ -2579,11 +2649,7 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
         const DgradP<uint16_t> p = dgrad_params<uint16_t>(a, packed, g, pl, gt, drop_s, flags);
         // resident-A kernel: 64-row workgroups, two per CU; below 256 rows per CU (a P = 8 rank's 20,000 rows: 313
         // workgroups) they underfill the GPU and the per-n-tile kernel's N / 128 times as many workgroups run faster
-        int dev = 0, ncu = 256;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-            ncu = 256;
-        const bool big = a->M >= (int64_t)256 * ncu;
+        const bool big = a->M >= (int64_t)256 * pg::cu_count();
         if (F_out <= RB_FMAX && F_out % BKB == 0 && !(flags & PG_FLAG_DGRAD_BF16_TILED) &&
             (big || (flags & PG_FLAG_DGRAD_BF16_RESIDENT))) {
             const int64_t nb = (a->M + RB_BM - 1) / RB_BM;
@@ -2593,27 +2659,8 @@ int pg_directgcn_dense_bwd_bf16(const pg_layer_args_t* a, const float* packed, c
             hipLaunchKernelGGL((dgrad_bf16_kernel<DG_BM, DG_BN, DG_NW>), dim3((unsigned)nb), dim3(64 * DG_NW), 0, s, p);
         }
     }
-    {
-        const int nb = (int)std::min<int64_t>((a->M + 255) / 256, 2048);
-        hipLaunchKernelGGL(gate_grad_kernel, dim3(nb), dim3(256), 0, s, a->M, pl.ntn, (const float*)dsp, gt, g->dgate);
-    }
-    {
-        const WgradP<uint16_t> w = wgrad_params<uint16_t>(a, g, pl);
-        if (bfs) {
-            const int tiles = (F_out / WX_BP) * (3 * F_in / WX_BN);
-            const unsigned nb = (unsigned)(8 * ((pl.splits + 7) / 8) * tiles);
-            hipLaunchKernelGGL(wgrad_bfs_kernel, dim3(nb), dim3(512), 0, s, w, (int)pl.splits);
-            if (proj) {  // the residual's columns [3 F_in, 4 F_in): the same partial buffers, no bias sums
-                WgradP<uint16_t> wr = w;
-                wr.col0 = 3 * F_in;
-                dim3 grid((unsigned)((F_in + 127) / 128), (unsigned)((F_out + 127) / 128), (unsigned)pl.splits);
-                hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(512), 0, s, wr);
-            }
-        } else {
-            dim3 grid((unsigned)((K + 127) / 128), (unsigned)((F_out + 127) / 128), (unsigned)pl.splits);
-            hipLaunchKernelGGL(wgrad_bf16_kernel, grid, dim3(512), 0, s, w);
-        }
-    }
+    launch_gate_grad(a->M, pl.ntn, dsp, gt, g->dgate, s);
+    launch_wgrad(wgrad_params<uint16_t>(a, g, pl), pl.splits, bfs, proj ? F_in : 0, s);
     launch_reduce(pl.part_stride / 4, pl.splits, pl.part_stride, part, g->dW, s);
     return pg::check_launch("pg_directgcn_dense_bwd_bf16");
 }

@@ -547,7 +547,8 @@ def _dense_case(M, Fin, Fout, proj, vec, rows, seed):
                                                       (5000, 32, 32, False, True, False), (300, 18, 10, True, True, False),
                                                       (257, 7, 5, True, True, False), (100, 13, 30, False, True, True),
                                                       (64, 6, 9, True, False, False), (2000, 256, 256, False, True, False),
-                                                      (1500, 128, 256, False, True, True), (20, 128, 128, False, True, False)])
+                                                      (1500, 128, 256, False, True, True), (20, 128, 128, False, True, False),
+                                                      (2050, 256, 256, False, True, False)])
 def test_dense_backward_vs_float64(pkg, cuda, M, Fin, Fout, proj, vec, rows):
     """Autograd of the fused dense layer (pg_directgcn_dense_bwd_f32: the MFMA kernels, or its any-shape kernels
     when F_in / F_out are not multiples of 4) against float64 autograd of protgram_directgcn.py:100-133 + residual
@@ -873,7 +874,8 @@ def test_head_bf16_input_equals_widened(pkg, cuda, F, H, C):
 
 @pytest.mark.parametrize("M,Fin,Fout,proj,vec,rows", [(1000, 128, 128, False, True, False), (777, 64, 128, True, True, True),
                                                       (300, 32, 16, False, False, False), (5000, 256, 256, False, True, False),
-                                                      (129, 16, 40, True, True, True), (300, 20, 12, True, True, False)])
+                                                      (129, 16, 40, True, True, True), (300, 20, 12, True, True, False),
+                                                      (2050, 256, 256, False, True, False)])
 def test_dense_backward_bf16_vs_float64(pkg, cuda, M, Fin, Fout, proj, vec, rows, drop=0.0):
     """bf16-mode autograd of the dense layer (pg_directgcn_dense_bwd_bf16; the last case, F not a multiple of 8,
     runs the fp32 backward kernels on widened copies) against float64 autograd on the same bf16-valued activations, with the leaky_relu
@@ -939,6 +941,14 @@ def test_dense_backward_bf16_vs_float64(pkg, cuda, M, Fin, Fout, proj, vec, rows
     if proj:
         close(Wrg.grad, Wrd.grad, "dW_res")
         close(brg.grad, brd.grad, "db_res")
+
+
+def test_dense_backward_bf16_tiled_wgrad_vs_float64(pkg, cuda, monkeypatch):
+    """The tiled bf16 weight gradient (PG_FLAG_WGRAD_BF16_TILED: wgrad_bf16_kernel instead of the default staged
+    wgrad_bfs_kernel at this shape) through the same bf16 float64 autograd check."""
+    from protgram_directgcn_amd._lib import PG_FLAG_WGRAD_BF16_TILED
+    monkeypatch.setenv("PG_SPMM_FLAGS", hex(PG_FLAG_WGRAD_BF16_TILED))
+    test_dense_backward_bf16_vs_float64(pkg, cuda, 1000, 128, 128, False, True, False)
 
 
 @pytest.mark.parametrize("M,Fin,Fout,proj,vec,rows", [(5000, 256, 256, False, True, False), (1000, 128, 256, True, True, True),

@@ -1,0 +1,169 @@
+"""Bit-identity probe of the dense backward between two builds of the library (a refactor's parent and its branch).
+
+    python tools/dense_bwd_bits.py PARENT_LIB BRANCH_LIB [--out FILE] [--dir DIR] [--timeout SECONDS]
+
+For each library one fresh child process (PG_DIRECTGCN_LIB set to it) runs the case list below on the seeded
+tests/test_gpu_parity._dense_case inputs, every case with dropout 0 and 0.3, and writes the bytes of every tensor
+ops.layer_dense_backward / ops.gemm_at_b returns under DIR/<parent|branch>/. This process then compares the two sets on
+the host (it never opens the GPU) and prints one `equal` / `DIFFERS` line per tensor and a count; exit status 0 only
+when every tensor is byte-equal. Each child has its own time limit; after a child that exits abnormally nothing more
+is started.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DROPS = (0.0, 0.3)
+
+# flags by name (protgram_directgcn_amd._lib); bf16: bf16 operands (pg_directgcn_dense_bwd_bf16);
+# span: e_res of pg_directgcn_dense_bwd_span_f32; the staged kernels take F_in, F_out % 128 == 0 without `proj`
+CASES = [
+    # staged fp32 (wgrad_x3_kernel, 16-row steps)
+    dict(name="x3_20x128", M=20, Fin=128, Fout=128),                 # 2 splits, the last of 4 rows
+    dict(name="x3_1000x128", M=1000, Fin=128, Fout=128),             # 63 splits on 64 workgroups: one idle (tile = -1)
+    dict(name="x3_2050x256", M=2050, Fin=256, Fout=256),             # 4 tiles, 43 splits of 48 rows (3 steps), last 34
+    dict(name="x3_1500x128to256", M=1500, Fin=128, Fout=256, rows=True),  # pt = 1
+    dict(name="x3_span_eres0", M=1000, Fin=128, Fout=128, span=0),
+    dict(name="x3_span_eres1", M=1000, Fin=128, Fout=128, span=1),
+    # PG_FLAG_WGRAD_F32MFMA: wgrad_kernel at staged shapes
+    dict(name="f32mfma_1000x128", M=1000, Fin=128, Fout=128, flags=("PG_FLAG_WGRAD_F32MFMA",)),
+    dict(name="f32mfma_3001x128_rows", M=3001, Fin=128, Fout=128, rows=True, flags=("PG_FLAG_WGRAD_F32MFMA",)),
+    # tiled fp32 (wgrad_kernel)
+    dict(name="tiled_777x64to128_proj_rows", M=777, Fin=64, Fout=128, proj=True, rows=True),
+    dict(name="tiled_513x20to12_proj", M=513, Fin=20, Fout=12, proj=True),
+    dict(name="tiled_64x128to96_rows", M=64, Fin=128, Fout=96, rows=True),
+    # any-shape kernels
+    dict(name="any_257x7to5_proj", M=257, Fin=7, Fout=5, proj=True),
+    # ops.gemm_at_b (null gates, one segment)
+    dict(name="gemm_33x4x8", gemm=(33, 4, 8)),
+    dict(name="gemm_1000x128x384", gemm=(1000, 128, 384)),
+    dict(name="gemm_70001x256x132", gemm=(70001, 256, 132)),
+    # staged bf16 (wgrad_bfs_kernel, 32-row steps)
+    dict(name="bfs_1000x128", M=1000, Fin=128, Fout=128, bf16=True),
+    dict(name="bfs_2050x256", M=2050, Fin=256, Fout=256, bf16=True),  # 48-row splits: the second step half empty
+    dict(name="bfs_5000x256", M=5000, Fin=256, Fout=256, bf16=True),  # three steps
+    dict(name="bfs_1000x128to256_proj_rows", M=1000, Fin=128, Fout=256, proj=True, rows=True, bf16=True),  # + col0 launch
+    dict(name="bfs_1000x128_dpre32", M=1000, Fin=128, Fout=128, bf16=True, dpre_f32=True),
+    dict(name="bfs_1000x128_resident", M=1000, Fin=128, Fout=128, bf16=True, flags=("PG_FLAG_DGRAD_BF16_RESIDENT",)),
+    # tiled bf16 (wgrad_bf16_kernel)
+    dict(name="bf16tiled_777x64to128_proj_rows", M=777, Fin=64, Fout=128, proj=True, rows=True, bf16=True),
+    dict(name="bf16tiled_1000x128_flag", M=1000, Fin=128, Fout=128, bf16=True, flags=("PG_FLAG_WGRAD_BF16_TILED",)),
+]
+
+
+def child(outdir: str) -> int:
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import torch
+    from __graft_entry__ import load_package
+    load_package()
+    from protgram_directgcn_amd import _lib, ops
+    from test_gpu_parity import _dense_case
+
+    dev = torch.device("cuda:0")
+    os.makedirs(outdir, exist_ok=True)
+
+    def save(case, drop, key, t):
+        t = t.detach().contiguous().cpu()
+        t.view(torch.uint8).numpy().tofile(os.path.join(outdir, f"{case}.drop{drop}.{key}.bin"))
+
+    for c in CASES:
+        if "gemm" in c:  # no dropout in a plain product: once
+            M, P, N = c["gemm"]
+            g = torch.Generator().manual_seed(M + P + N)
+            A, B = torch.randn(M, P, generator=g), torch.randn(M, N, generator=g)
+            C, cs = ops.gemm_at_b(A.to(dev), B.to(dev))
+            save(c["name"], 0.0, "C", C)
+            save(c["name"], 0.0, "colsum", cs)
+            continue
+        M, Fin, Fout = c["M"], c["Fin"], c["Fout"]
+        proj, rows, bf = c.get("proj", False), c.get("rows", False), c.get("bf16", False)
+        Z, xres, prm, const, r, W_res, b_res, dY = _dense_case(M, Fin, Fout, proj, True, rows, 7 * M + Fin)
+        cast = (lambda t: t.to(dev).to(torch.bfloat16)) if bf else (lambda t: t.to(dev))
+        prm = {k: v.to(dev) for k, v in prm.items()}
+        Zg, dYg = cast(Z), cast(dY)
+        xg = cast(xres) if xres is not None else None
+        rg = r.to(dev) if r is not None else None
+        Wr, br = (W_res.to(dev), b_res.to(dev)) if proj else (None, None)
+        fl = ops.default_flags()
+        for f in c.get("flags", ()):
+            fl |= getattr(_lib, f)
+        for drop in DROPS:
+            seed = torch.tensor([0x0123_4567_89AB_CDEF + M], dtype=torch.int64, device=dev)
+            packs = [] if bf else None
+            Y = ops.layer_dense(Zg, prm, 0, rows=rg, res_x=xg, W_res=Wr, b_res=br, act=True, flags=fl, packs=packs,
+                                drop=(drop, seed) if drop else None)
+            span = None
+            if "span" in c:
+                wd = torch.rand(M, 3, generator=torch.Generator().manual_seed(M)).to(dev)
+                span = (wd, c["span"])
+            out = ops.layer_dense_backward(dYg, Zg, Y, prm, 0, rows=rg, res_x=xg, W_res=Wr, b_res=br, act=True,
+                                           flags=fl, packs=packs or None, span=span, drop_p=drop,
+                                           dpre_f32=c.get("dpre_f32", False))
+            if out is None:
+                print(f"{c['name']}: the entry point does not take this case", file=sys.stderr)
+                return 2
+            for key, t in out.items():
+                if t is not None:
+                    save(c["name"], drop, key, t)
+    torch.cuda.synchronize()
+    return 0
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("parent_lib")
+    ap.add_argument("branch_lib")
+    ap.add_argument("--out", help="also write the report to this file")
+    ap.add_argument("--dir", default=os.path.join(tempfile.gettempdir(), "dense_bwd_bits"), help="tensor dumps")
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
+    ap.add_argument("--child", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child)
+    dirs = {}
+    for tag, lib in (("parent", a.parent_lib), ("branch", a.branch_lib)):
+        dirs[tag] = os.path.join(a.dir, tag)
+        shutil.rmtree(dirs[tag], ignore_errors=True)  # no dumps of an earlier run
+        env = dict(os.environ, PG_DIRECTGCN_LIB=os.path.abspath(lib))
+        env.pop("PG_SPMM_FLAGS", None)
+        try:
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--child", dirs[tag]], env=env,
+                                timeout=a.timeout).returncode
+        except subprocess.TimeoutExpired:
+            rc = 124
+        if rc != 0:
+            print(f"dense_bwd_bits: the {tag} child ({lib}) ended with status {rc}; nothing more started",
+                  file=sys.stderr)
+            return 1
+    names = sorted(set(os.listdir(dirs["parent"])) | set(os.listdir(dirs["branch"])))
+    lines, bad = [], 0
+    for n in names:
+        pa, pb = os.path.join(dirs["parent"], n), os.path.join(dirs["branch"], n)
+        if not (os.path.exists(pa) and os.path.exists(pb)):
+            verdict = "DIFFERS (missing in one build)"
+        else:
+            with open(pa, "rb") as fa, open(pb, "rb") as fb:
+                da, db = fa.read(), fb.read()
+            verdict = "equal" if da == db else "DIFFERS"
+            verdict += f"  {len(da)} bytes"
+        bad += not verdict.startswith("equal")
+        lines.append(f"{n[:-4]:60s} {verdict}")
+    lines.append(f"{len(names)} tensors of {len(CASES)} cases (dropout {DROPS[0]} and {DROPS[1]}): "
+                 f"{len(names) - bad} equal, {bad} DIFFERS")
+    report = "\n".join(lines)
+    print(report)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(f"parent {a.parent_lib}\nbranch {a.branch_lib}\n{report}\n")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
