@@ -497,6 +497,31 @@ int pg_directgcn_head_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uin
 int pg_ngram_keys(int64_t nseq, const int64_t* offsets, const uint8_t* bytes, const int32_t* lut, int n,
                   int64_t K, int64_t* keys, int64_t* next_keys, void* stream);
 
+/* ---- closest_aa task labels (protgram_directgcn_trainer.py:239-269, _generate_closest_amino_acid_labels) as a
+ * k-hop reach of letter bitmasks -------------------------------------------------------------------------------
+ * Letters of every node: masks[i] = OR over the n base-K digits d of node_keys[i] (keys as pg_ngram_keys makes
+ * them) of 1 << code_bit[d]. code_bit [K]: the bit of alphabet character d, in [0, 32), or -1 for a character
+ * that is no letter (' ', X, U, ...). A negative key gives 0. n >= 1, K >= 1 and K^n must fit 63 bits (PG_ERR_ARG
+ * otherwise, pg_ngram_keys' rule); n_nodes = 0: PG_OK, nothing is launched or read. */
+int pg_ngram_letter_masks(int64_t n_nodes, const int64_t* node_keys, int n, int64_t K, const int32_t* code_bit,
+                          uint32_t* masks, void* stream);
+
+/* One hop over a CSR of out-edges (rowptr int64 [n_rows + 1], col int64 [rowptr[n_rows]]):
+ *   reach_out[v] = reach_in[v] | OR_{e in [rowptr[v], rowptr[v+1])} reach_in[col[e]]
+ * and, with fresh = reach_out[v] & ~reach_in[v] (the bits this hop brought):
+ *   dist[v * ldd + b] = hop  for every bit b < n_bits of fresh   (dist given: uint8, row stride ldd >= n_bits);
+ *   labels[v] = hop          if bit target[v] is in fresh        (target uint8 [n_rows] and labels int64 [n_rows]
+ *                                                                 given, both or neither; target[v] >= 32: never).
+ * Nothing else is written: the caller initialises dist / labels for hop 0 (0 where the node's own mask has the
+ * bit, else the clip value k) and calls hops 1..k with reach_in / reach_out swapped in between. Integer OR: the
+ * same bits whatever the order. PG_ERR_ARG for n_rows outside [0, 2^31), hop outside [1, 255], n_bits outside
+ * [1, 32], ldd < n_bits with dist, one of target / labels without the other, a null rowptr / col / reach_in /
+ * reach_out with n_rows > 0, and reach_in overlapping reach_out (in place a launch could carry a bit two hops).
+ * col entries must lie in [0, n_rows): the kernel does not check them, the caller does. */
+int pg_reach_hop_u32(int64_t n_rows, const int64_t* rowptr, const int64_t* col, const uint32_t* reach_in,
+                     uint32_t* reach_out, int hop, int n_bits, uint8_t* dist, int64_t ldd, const uint8_t* target,
+                     int64_t* labels, void* stream);
+
 /* ---- protein-level pooling (protgram_directgcn_trainer.py:387-398, "Step 3: Pooling N-gram Embeddings to
  * Protein Level") ---------------------------------------------------------------------------------------------
  * Node id of every window: the ngram_map.get("".join(seq[i:i + n])) of models_utils.py:202 and :238-239. For

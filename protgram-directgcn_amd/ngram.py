@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import random
 from dataclasses import dataclass
 from typing import Iterator, List, Optional, Sequence, Tuple
 
@@ -321,3 +322,195 @@ def pool_features(cur: NgramTransitions, prev: NgramTransitions, emb_prev: torch
     only_s = sok & ~pok
     x[only_s] = emb_prev[si[only_s]]
     return x
+
+
+# ------------------------------------------------------------------------------------------------------------
+# closest_aa task labels (protgram_directgcn_trainer.py:239-269) as a k-hop reach of letter bitmasks
+# (csrc/pg_labels.hip)
+# ------------------------------------------------------------------------------------------------------------
+
+AMINO_ACIDS = "ACDEFGHIKLMNPQRSTVWY"  # the trainer's AMINO_ACID_ALPHABET order: bit / index b is letter b
+
+
+def _vp(t: torch.Tensor):
+    return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check_letters(letters: str) -> str:
+    letters = "".join(letters)
+    if len(letters) < 1 or len(letters) > 32:
+        raise ValueError("letters must hold 1 to 32 characters (one bit of a 32-bit mask each)")
+    if len(set(letters)) != len(letters):
+        raise ValueError("letters must not repeat a character")
+    return letters
+
+
+def _level_device(t: NgramTransitions, what: str) -> torch.device:
+    dev = t.src.device
+    if dev.type != "cuda" or t.dst.device != dev:
+        raise RuntimeError(f"{what} runs on the MI355X only: the level's tensors must be on the GPU (no CPU fallback)")
+    return dev
+
+
+def letter_masks(t: NgramTransitions, letters: str = AMINO_ACIDS) -> torch.Tensor:
+    """uint32 [N] on t.src's device: bit b of entry i is set when node i's n-gram contains letters[b]. Characters of
+    t.alphabet outside `letters` (' ', X, U, ...) set no bit."""
+    letters = _check_letters(letters)
+    dev = _level_device(t, "letter_masks")
+    N, n, K = int(t.num_nodes), int(t.n), max(len(t.alphabet), 1)
+    masks = torch.empty(N, dtype=torch.uint32, device=dev)
+    if N == 0:
+        return masks
+    if n < 1 or n * math.log2(K) >= 62.5:
+        raise ValueError(f"{K}^{n} windows do not fit a 64-bit key")
+    keys = t.node_keys.to(dev).contiguous()
+    if keys.dtype != torch.int64 or keys.shape != (N,):
+        raise ValueError("node_keys must be int64 [num_nodes]")
+    if int(keys.min()) < 0 or int(keys.max()) >= K ** n:
+        raise IndexError(f"node_keys outside [0, {K}^{n})")
+    bit = {ch: b for b, ch in enumerate(letters)}
+    code_bit = torch.tensor([bit.get(ch, -1) for ch in t.alphabet] or [-1], dtype=torch.int32).to(dev)
+    check(load_library().pg_ngram_letter_masks(N, _vp(keys), n, K, _vp(code_bit), _vp(masks), _stream(dev)),
+          "pg_ngram_letter_masks")
+    return masks
+
+
+def _out_csr(t: NgramTransitions, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(rowptr int64 [N + 1], col int64 [E]) of the out-edges; t.src is sorted (the dataclass's contract), so the
+    row pointer is the running sum of its counts, as graph._rowptr builds it. Every endpoint is checked here: the hop
+    kernel gathers reach[col[e]] unguarded."""
+    N = int(t.num_nodes)
+    src, dst = t.src.contiguous(), t.dst.contiguous()
+    if src.dtype != torch.int64 or dst.dtype != torch.int64 or src.dim() != 1 or src.shape != dst.shape:
+        raise ValueError("src and dst must be int64 [E]")
+    if src.numel():
+        if int(dst.min()) < 0 or int(dst.max()) >= N:
+            raise IndexError(f"dst outside [0, {N})")
+        if int(src.min()) < 0 or int(src.max()) >= N:
+            raise IndexError(f"src outside [0, {N})")
+        if src.numel() > 1 and bool((src[1:] < src[:-1]).any()):
+            raise ValueError("src must be sorted (NgramTransitions keeps its edges ordered by (src, dst))")
+    rowptr = torch.zeros(N + 1, dtype=torch.int64, device=dev)
+    if src.numel():
+        torch.cumsum(torch.bincount(src, minlength=N), 0, out=rowptr[1:])
+    return rowptr, dst
+
+
+def _check_hops(k_hops) -> int:
+    k = int(k_hops)
+    if k != k_hops or k < 0 or k > 255:
+        raise ValueError("k_hops must be an integer in [0, 255]")
+    return k
+
+
+def _own_bits(masks: torch.Tensor, n_bits: int) -> torch.Tensor:
+    """bool [N, n_bits]: the bits of the uint32 masks."""
+    shifts = torch.arange(n_bits, dtype=torch.int32, device=masks.device)
+    return ((masks.view(torch.int32).unsqueeze(1) >> shifts) & 1).bool()
+
+
+def _hops(rowptr, col, masks, k, n_bits, dist=None, target=None, labels=None):
+    """Hops 1..k of pg_reach_hop_u32 with two reach buffers that swap roles."""
+    lib = load_library()
+    dev = masks.device
+    N = masks.numel()
+    cur, nxt = masks, torch.empty_like(masks)
+    if k > 1:
+        cur = masks.clone()  # the caller's masks stay as they are
+    for h in range(1, k + 1):
+        # an empty col has no address: every row is empty then and any non-null pointer stands in for it
+        check(lib.pg_reach_hop_u32(N, _vp(rowptr), _vp(col) or _vp(rowptr), _vp(cur), _vp(nxt), h, n_bits,
+                                   _vp(dist) if dist is not None else None, n_bits,
+                                   _vp(target) if target is not None else None,
+                                   _vp(labels) if labels is not None else None, _stream(dev)), "pg_reach_hop_u32")
+        cur, nxt = nxt, cur
+
+
+def letter_distances(t: NgramTransitions, k_hops: int, letters: str = AMINO_ACIDS) -> torch.Tensor:
+    """uint8 [N, len(letters)]: entry (v, b) = min(k_hops, length of the shortest out-path from node v to a node whose
+    n-gram contains letters[b]), 0 when v's own n-gram contains it. k_hops launches of the hop kernel."""
+    letters = _check_letters(letters)
+    k = _check_hops(k_hops)
+    dev = _level_device(t, "letter_distances")
+    N, L = int(t.num_nodes), len(letters)
+    if N == 0:
+        return torch.empty(0, L, dtype=torch.uint8, device=dev)
+    rowptr, col = _out_csr(t, dev)
+    masks = letter_masks(t, letters)
+    dist = torch.full((N, L), k, dtype=torch.uint8, device=dev)
+    dist[_own_bits(masks, L)] = 0
+    _hops(rowptr, col, masks, k, L, dist=dist)
+    return dist
+
+
+def draw_targets(num_nodes: int, letters: str = AMINO_ACIDS, rng=None) -> List[int]:
+    """One target letter index per node, drawn as the trainer draws them (protgram_directgcn_trainer.py:247):
+    rng.choice(list(letters)) once per node in node order, on the host; `rng` defaults to the `random` module, so
+    random.seed(s) before the call gives the reference's sequence."""
+    rng = random if rng is None else rng
+    index = {ch: b for b, ch in enumerate(letters)}
+    pool = list(letters)
+    return [index[rng.choice(pool)] for _ in range(num_nodes)]
+
+
+def _target_indices(targets, N: int, letters: str, rng) -> torch.Tensor:
+    """uint8 [N] on the host: the drawn or given target letter index per node."""
+    index = {ch: b for b, ch in enumerate(letters)}
+    if targets is None:
+        idx = draw_targets(N, letters, rng)
+    elif isinstance(targets, str):
+        try:
+            idx = [index[ch] for ch in targets]
+        except KeyError as e:
+            raise ValueError(f"target letter {e.args[0]!r} is not one of the letters") from None
+    elif torch.is_tensor(targets):
+        idx = targets.detach().cpu().to(torch.int64).reshape(-1)
+    else:
+        idx = [int(x) for x in targets]
+    idx = torch.as_tensor(idx, dtype=torch.int64).reshape(-1)
+    if idx.numel() != N:
+        raise ValueError(f"targets must have one entry per node ({N}), got {idx.numel()}")
+    if N and (int(idx.min()) < 0 or int(idx.max()) >= len(letters)):
+        raise ValueError(f"target indices must lie in [0, {len(letters)})")
+    return idx.to(torch.uint8)
+
+
+def closest_aa_labels(t: NgramTransitions, k_hops: int = 3, targets=None, rng=None,
+                      letters: str = AMINO_ACIDS) -> Tuple[torch.Tensor, int]:
+    """The trainer's closest_aa task labels (protgram_directgcn_trainer.py:239-269) for all nodes at once: per node a
+    target letter, label = the number of hops along out-edges to the nearest node whose n-gram contains it (0: the
+    node itself), k_hops when none is within k_hops; num_classes = k_hops + 1. targets=None draws
+    rng.choice(list(letters)) per node in node order on the host (`rng`: the `random` module by default), the
+    reference's own draw sequence: after random.seed(s) the labels are the reference's. Otherwise `targets` holds one
+    letter index per node (sequence or tensor) or is a str of N letters."""
+    letters = _check_letters(letters)
+    k = _check_hops(k_hops)
+    dev = _level_device(t, "closest_aa_labels")
+    N = int(t.num_nodes)
+    if N == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), k + 1
+    tgt = _target_indices(targets, N, letters, rng)
+    rowptr, col = _out_csr(t, dev)
+    masks = letter_masks(t, letters)
+    tgt = tgt.to(dev)
+    own = (masks.view(torch.int32) >> tgt.to(torch.int32)) & 1
+    labels = torch.where(own.bool(), 0, k).to(torch.int64)
+    _hops(rowptr, col, masks, k, len(letters), target=tgt, labels=labels)
+    return labels, k + 1
+
+
+def task_labels(t: NgramTransitions, task: str, **kw) -> Tuple[torch.Tensor, int]:
+    """(labels, num_classes) of one of the trainer's self-supervised tasks (GCN_TASK_TYPES_PER_LEVEL,
+    protgram_directgcn_trainer.py:333-341)."""
+    if task == "next_node":
+        return next_node_labels(t, **kw)
+    if task == "closest_aa":
+        return closest_aa_labels(t, **kw)
+    if task == "community":
+        raise ValueError("task 'community' needs a Louvain partition, which is out of scope here (DESIGN §7): the "
+                         "caller supplies those labels")
+    raise ValueError(f"Unsupported GCN_TASK_TYPE '{task}' for n={t.n}.")
