@@ -29,7 +29,7 @@ using pgbf::pack8;
 using pgbf::unpack8;
 __device__ __forceinline__ float bf_lo(uint32_t w) { return pgbf::lo(w); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return pgbf::hi(w); }
-__device__ __forceinline__ float fb(int v) { return __int_as_float(v); }
+using pg::fb;
 
 // ------------------------------------------------------------------------------------------------
 // SpMM, record-window variant (pg_spmm.hip variant C) over bf16 rows: LPR lanes x 8 features per row.
@@ -203,8 +203,6 @@ struct DenseB {
     float drop_s;
     const int64_t* drop_seed;
 };
-
-__device__ __forceinline__ float4 ld4f(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 template <int BM, int BN, int NW>
 __global__ __launch_bounds__(64 * NW) void dense_bf16_kernel(DenseB p) {
@@ -380,7 +378,7 @@ __global__ __launch_bounds__(64 * NW) void dense_bf16_kernel(DenseB p) {
         float o[4] = {v.x, v.y, v.z, v.w};
         float cc[4] = {0.f, 0.f, 0.f, 0.f}, rr[4] = {0.f, 0.f, 0.f, 0.f};
         if (has_const) {
-            const float4 c = ld4f(p.constant + Crow[rl] * p.ld_const + nb);
+            const float4 c = pg::ld4(p.constant + Crow[rl] * p.ld_const + nb);
             cc[0] = c.x; cc[1] = c.y; cc[2] = c.z; cc[3] = c.w;
         }
         if (id_res) {

@@ -15,6 +15,9 @@ namespace pg {
 int set_error(int code, const char* fmt, ...);
 void clear_error();
 
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }  // 16-B aligned
+__device__ __forceinline__ float fb(int v) { return __int_as_float(v); }
+
 // XCD-contiguous logical block index. The dispatcher deals workgroups round-robin over the 8 XCDs
 // (blocks b and b+8 share an XCD, MI355X_MICROARCH.md "Workgroup dispatch"); remapping gives each
 // XCD one contiguous range of row blocks so the rows that share neighbour lists share an L2.

@@ -25,6 +25,7 @@
 // lane feeds its MFMAs with one ds_read_b128 per operand per 4 MFMAs by permuting K identically for A
 // and B inside each group of 8 (MFMA k-step s of lane half h uses k = 4h + s): same sum, other order.
 #include "pg_common.h"
+#include "pg_lds.h"
 #include "pg_split3.h"
 
 namespace {
@@ -122,7 +123,7 @@ __device__ __forceinline__ int64_t ngram_row(const DenseP& p, int64_t m) {
     return (int64_t)a * p.map_kn1 + (p.map_m0 + q) * 20 + b;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using pg::ld4;
 __device__ __forceinline__ float4 scale4(float4 a, float s) { return make_float4(a.x * s, a.y * s, a.z * s, a.w * s); }
 
 __device__ __forceinline__ int seg_of(int k, int F) { return (k >= F) + (k >= 2 * F) + (k >= 3 * F); }
@@ -395,16 +396,16 @@ __global__ __launch_bounds__(64 * NW) void dense_kernel(DenseP p) {
 // Helpers of the W-stationary split-bf16 kernels below. Their tiles' A rows arrive by LDS-DMA
 // (global_load_lds_dwordx4, 1 KiB per wave-instruction, lane-linear) into images whose 16-byte chunks are
 // XOR-swizzled by row (chunk c of row r at c ^ (r & 15), set through the per-lane SOURCE address).
-// One LDS-DMA piece: 16 B per lane from a per-lane global address to (wave-uniform base + 16 * lane).
-__device__ __forceinline__ void glds16(const float* src, float* lds_base) {
-    __builtin_amdgcn_global_load_lds(src, lds_base, 16, 0, 0);
-}
-// the same with the non-temporal cache policy (aux = 2): the A rows and the per-node constant, read once (measured:
-// 0.5587 -> 0.5496 ms per bench step for the A rows, the next layer's propagation finding its input in cache, and
-// 0.550 -> 0.545 ms for the constant; PG_FLAG_DENSE_A_CACHED selects the default policy for both)
-__device__ __forceinline__ void glds16nt(const float* src, float* lds_base) {
-    __builtin_amdgcn_global_load_lds(src, lds_base, 16, 0, 2);
-}
+// The pieces, the LDS-only barrier and the reason for the counted waits: pg_lds.h. The A rows and the per-node
+// constant, read once, take the non-temporal piece (measured: 0.5587 -> 0.5496 ms per bench step for the A rows, the
+// next layer's propagation finding its input in cache, and 0.550 -> 0.545 ms for the constant;
+// PG_FLAG_DENSE_A_CACHED selects the default policy for both).
+using pg::glds16;
+using pg::glds16nt;
+using pg::glds4;
+using pg::lds_addr;
+using pg::lds_barrier;
+using pg::opaque;
 
 // epilogue sum of the W-stationary kernels with every rounding step explicit (no contraction choices left to the
 // compiler), so the 32-row and the pipelined 16-row split-bf16 kernels round identically:
@@ -434,18 +435,8 @@ using pgx3::bf2;
 using pgx3::mfma_bf;
 using pgx3::split8;
 
-// Workgroup barrier for LDS hand-offs only: drains this wave's LDS ops, not its global loads (__syncthreads'
-// release fence also waits vmcnt(0), which would drain the next tile's LDS-DMA in flight). LDS-DMA landings are
-// waited for explicitly with s_waitcnt vmcnt before the barriers that publish them.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// LDS reads of LDS-DMA targets through inline asm. hipcc cannot tell which LDS-DMA (counted in vmcnt) wrote the
-// bytes a ds_read touches, so before every such read it waits vmcnt(0) -- draining the DMA of the tiles in
-// flight. These reads carry their own lgkmcnt wait; the DMA they depend on is retired by the explicit counted
-// vmcnt waits + barriers of the tile loop.
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
+// LDS reads of LDS-DMA targets go through inline asm (pg_lds.h: hipcc would wait vmcnt(0) before them). They carry
+// their own lgkmcnt wait; the DMA they depend on is retired by the counted vmcnt waits + barriers of the tile loops.
 __device__ __forceinline__ void lds_ld4x2(const float* p0, const float* p1, float4& a, float4& b) {
     f32x4 x, y;
     asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
@@ -506,16 +497,78 @@ __device__ __forceinline__ void lds_gates5(const float* p, float (&g)[5]) {
         : "memory");
 }
 
-// One LDS-DMA piece of 4 B per lane (lanes write consecutive dwords from wave-uniform base lds_base).
-__device__ __forceinline__ void glds4(const float* src, float* lds_base) {
-    __builtin_amdgcn_global_load_lds(src, lds_base, 4, 0, 0);
-}
-
 // bf16 split image layout of one 32-row tile: [k step s][row r][4 units], unit g of row r stored at slot
 // g ^ ((-(r >> 2)) & 3). A wave's MFMA read of step s (lane: row lc or 16 + lc, unit kg) is then one per-lane
 // address plus s * 2 KB, and every ds_read_b128 lane group (0-3,12-15,20-27 | 4-11,16-19,28-31 | ...) and every
 // 8-lane ds_write_b128 group of the split pass hits 16 distinct 16-B bank slots.
 __device__ __forceinline__ int a_unit(int s, int r, int g) { return 128 * s + 4 * r + (g ^ ((-(r >> 2)) & 3)); }
+
+// ---------------------------------------------------------------------------------------------------------
+// Stages that dense_x3_kernel and dense_x3p_kernel share ("Dense forward source"); tile shapes, LDS
+// images, counted waits and loops are each kernel's own.
+// The tiles of this workgroup: lo, lo + step, ... (ntl of them) out of T. With a grid that is a multiple of 8, XCD x
+// (workgroups b with b % 8 == x) takes the contiguous range [T x / 8, T (x + 1) / 8) of tiles; else round-robin.
+struct TileRange { int64_t ntl, lo, step; };
+__device__ __forceinline__ TileRange tile_range(int64_t T) {
+    const int nb = gridDim.x, b = blockIdx.x;
+    TileRange t;
+    if ((nb & 7) == 0 && nb >= 8) {
+        const int x = b & 7, i = b >> 3, bpx = nb >> 3;
+        const int64_t xlo = T * x / 8, xhi = T * (x + 1) / 8;
+        t.ntl = (xhi - xlo - i + bpx - 1) / bpx;
+        t.lo = xlo + i;
+        t.step = bpx;
+    } else {
+        t.ntl = (T - b + nb - 1) / nb;
+        t.lo = b;
+        t.step = nb;
+    }
+    if (t.ntl < 0) t.ntl = 0;
+    return t;
+}
+
+// W splits of a lane from the packed weights: k step s uses fp32 chunks 8s + kg and 8s + kg + 4 of column `col`
+// (src = Bp + col K + 4 kg; the same k permutation as the A units)
+template <int NS>
+__device__ __forceinline__ void w_splits(const float* src, uint4 (&w0)[NS], uint4 (&w1)[NS], uint4 (&w2)[NS]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const float4 x0 = ld4(src + 32 * s), x1 = ld4(src + 32 * s + 16);
+        const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+        split8(v, w0[s], w1[s], w2[s]);
+    }
+}
+
+// s_in = c_all c_dir c_in, s_out = c_all c_dir c_out, s_und = c_all c_und (protgram_directgcn.py:116-133) from a
+// row's gate inputs c = {C_in, C_out, C_dir, C_und, C_all}
+__device__ __forceinline__ void gate_scales(const float (&c)[5], float& s0, float& s1, float& s2) {
+    const float cad = c[4] * c[2];
+    s0 = cad * c[0];
+    s1 = cad * c[1];
+    s2 = c[4] * c[3];
+}
+
+// The five gate pointers for issue_G's per-lane choice among them: by arithmetic on opaque copies (an indexed choice
+// among kernel arguments becomes a kernarg load, whose wait would drain the DMA in flight)
+__device__ __forceinline__ void gate_ptrs(const DenseP& p, const float* (&c)[5]) {
+    c[0] = p.C_in, c[1] = p.C_out, c[2] = p.C_dir, c[3] = p.C_und, c[4] = p.C_all;
+    asm volatile("" : "+s"(c[0]), "+s"(c[1]), "+s"(c[2]), "+s"(c[3]), "+s"(c[4]));
+}
+
+// Constant (cb) and residual (rb) row of row r (clamped to the last valid one) of a BM-row tile. An absent operand
+// fetches the tile's first Z row (valid, and zeroed in the epilogue), so that every wave issues the same number of
+// pieces or loads per tile. MAP: the kernel takes the n-gram row map (DenseP::map_res).
+template <bool MAP, int BM>
+__device__ __forceinline__ void cr_rows(const DenseP& p, bool has_const, bool id_res, int64_t tile, int r,
+                                        const float*& cb, const float*& rb) {
+    const int64_t m0 = tile * BM;
+    const int rmax = (int)min((int64_t)(BM - 1), p.M - 1 - m0);
+    const int rr = min(r, rmax);
+    cb = has_const ? p.constant + m0 * p.ld_const + (rr * (int)p.ld_const) : p.Z + m0 * p.ldz;
+    rb = !id_res            ? p.Z + m0 * p.ldz
+         : MAP && p.map_res ? p.res_x + ngram_row(p, m0 + rr) * p.ld_res
+                            : p.res_x + m0 * p.ld_res + (rr * (int)p.ld_res);
+}
 
 template <int F_IN, int KSEG, bool PRE>
 __global__ __launch_bounds__(512) void dense_x3_kernel(DenseP p) {
@@ -547,33 +600,10 @@ __global__ __launch_bounds__(512) void dense_x3_kernel(DenseP p) {
     const int col = 16 * wave + lc;
     const int64_t T = (p.M + BMW - 1) / BMW;
     Bs[tid >> 7][tid & 127] = (tid >> 7) < 3 || p.proj_res ? p.bsum[(tid >> 7) * p.F_out + (tid & 127)] : 0.f;
-    const int nb = gridDim.x, b = blockIdx.x;
-    int64_t ntl, lo, step;
-    if ((nb & 7) == 0 && nb >= 8) {  // XCD x takes a contiguous range of tiles
-        const int x = b & 7, i = b >> 3, bpx = nb >> 3;
-        const int64_t xlo = T * x / 8, xhi = T * (x + 1) / 8;
-        ntl = (xhi - xlo - i + bpx - 1) / bpx;
-        lo = xlo + i;
-        step = bpx;
-    } else {
-        ntl = (T - b + nb - 1) / nb;
-        lo = b;
-        step = nb;
-    }
-    if (ntl < 0) ntl = 0;
-
-    // W splits of this lane: k step s uses fp32 chunks 8s + kg and 8s + kg + 4 of column `col` (the same k
-    // permutation as the A units below)
+    const TileRange tr = tile_range(T);
+    const int64_t ntl = tr.ntl, lo = tr.lo, step = tr.step;
     uint4 w0[NS], w1[NS], w2[NS];
-    {
-        const float* src = p.Bp + (int64_t)col * K + 4 * kg;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const float4 x0 = ld4(src + 32 * s), x1 = ld4(src + 32 * s + 16);
-            const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-            split8(v, w0[s], w1[s], w2[s]);
-        }
-    }
+    w_splits<NS>(p.Bp + (int64_t)col * K + 4 * kg, w0, w1, w2);
     const int ej = tid & 31, er = tid >> 5;  // epilogue: columns [4ej, 4ej+4) of rows er and er + 16
     const bool has_const = p.constant && p.gate_mode == PG_GATES_VECTOR;
     const bool id_res = p.res_x && !p.proj_res;
@@ -589,8 +619,7 @@ __global__ __launch_bounds__(512) void dense_x3_kernel(DenseP p) {
         const int rmax = (int)min((int64_t)(BMW - 1), p.M - 1 - m0);
         const float* zb = p.Z + m0 * p.ldz;
         const float* xb = KSEG > 3 ? p.res_x + m0 * p.ld_res : zb;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
+        const int ln = opaque(lane);
 #pragma unroll
         for (int i = 0; i < NI; ++i) {
             const int idx = (wave * NI + i) * 64 + ln;
@@ -604,46 +633,30 @@ __global__ __launch_bounds__(512) void dense_x3_kernel(DenseP p) {
     };
     // gate inputs of the tile's rows (wave 0 only): piece i, lanes 0-31 / 32-63 fetch C_x for x = 2i / 2i + 1
     auto issue_G = [&](int64_t tile, int gbuf) {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
+        const int ln = opaque(lane);
         const int64_t r = p.gate_mode == PG_GATES_SCALAR ? 0 : min(tile * BMW + (ln & 31), p.M - 1);
-        // per-lane choice among uniform pointers by arithmetic (an indexed choice becomes a kernarg load, whose
-        // wait would drain the DMA in flight)
-        const float* c0 = p.C_in;
-        const float* c1 = p.C_out;
-        const float* c2 = p.C_dir;
-        const float* c3 = p.C_und;
-        const float* c4 = p.C_all;
-        asm volatile("" : "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3), "+s"(c4));
+        const float* c[5];
+        gate_ptrs(p, c);
         const bool hi = ln >= 32;
-        glds4((hi ? c1 : c0) + r, &Gi[gbuf][0][0]);
-        glds4((hi ? c3 : c2) + r, &Gi[gbuf][2][0]);
-        glds4(c4 + r, &Gi[gbuf][4][0]);
+        glds4((hi ? c[1] : c[0]) + r, &Gi[gbuf][0][0]);
+        glds4((hi ? c[3] : c[2]) + r, &Gi[gbuf][2][0]);
+        glds4(c[4] + r, &Gi[gbuf][4][0]);
     };
     auto issue_CR = [&](int64_t tile) {
-        const int64_t m0 = tile * BMW;
-        const int rmax = (int)min((int64_t)(BMW - 1), p.M - 1 - m0);
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
+        const int ln = opaque(lane);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {  // wave w: rows 4w .. 4w + 3
             const int piece = 2 * wave + i;
-            const int rr = min(2 * piece + (ln >> 5), rmax);
-            const float* cb = has_const ? p.constant + m0 * p.ld_const + (rr * (int)p.ld_const) : p.Z + m0 * p.ldz;
-            const float* rb = id_res ? p.res_x + m0 * p.ld_res + (rr * (int)p.ld_res) : p.Z + m0 * p.ldz;
+            const float *cb, *rb;
+            cr_rows<false, BMW>(p, has_const, id_res, tile, 2 * piece + (ln >> 5), cb, rb);
             glds16(cb + 4 * (ln & 31), Cs + piece * 256);
             glds16(rb + 4 * (ln & 31), Rs + piece * 256);
         }
     };
-    // s_in = c_all c_dir c_in, s_out = c_all c_dir c_out, s_und = c_all c_und (protgram_directgcn.py:116-133)
     auto gates = [&](int gbuf, int r, float& s0, float& s1, float& s2) {
         float c[5];
         lds_gates5<BMW * 4>(&Gi[gbuf][0][r], c);
-        const float ci = c[0], co = c[1], cd = c[2], cu = c[3], ca = c[4];
-        const float cad = ca * cd;
-        s0 = cad * ci;
-        s1 = cad * co;
-        s2 = ca * cu;
+        gate_scales(c, s0, s1, s2);
     };
     auto tile_of = [&](int64_t kt) { return lo + min(kt, ntl - 1) * step; };  // clamped: dummy tiles past the end
 
@@ -839,20 +852,8 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
         }
         Bs[q][n] = bv;
     }
-    const int nb = gridDim.x, b = blockIdx.x;
-    int64_t ntl, lo, step;
-    if ((nb & 7) == 0 && nb >= 8) {  // XCD x takes a contiguous range of tiles
-        const int x = b & 7, i = b >> 3, bpx = nb >> 3;
-        const int64_t xlo = T * x / 8, xhi = T * (x + 1) / 8;
-        ntl = (xhi - xlo - i + bpx - 1) / bpx;
-        lo = xlo + i;
-        step = bpx;
-    } else {
-        ntl = (T - b + nb - 1) / nb;
-        lo = b;
-        step = nb;
-    }
-    if (ntl < 0) ntl = 0;
+    const TileRange tr = tile_range(T);
+    const int64_t ntl = tr.ntl, lo = tr.lo, step = tr.step;
 
     uint4 w0[NS], w1[NS], w2[NS];
     if (p.rawW) {  // W_q + W_shared, k step s lies in segment q = s / 4
@@ -866,13 +867,7 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
             split8(v, w0[s], w1[s], w2[s]);
         }
     } else {
-        const float* src = p.Bp + (int64_t)col * K + 4 * kg;
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const float4 x0 = ld4(src + 32 * s), x1 = ld4(src + 32 * s + 16);
-            const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-            split8(v, w0[s], w1[s], w2[s]);
-        }
+        w_splits<NS>(p.Bp + (int64_t)col * K + 4 * kg, w0, w1, w2);
     }
     // epilogue: columns [ec, ec + 4) of tile row er -- the lane's own accumulators, or (LDSE) a float4 of the Es tile
     const int ec = LDSE ? 4 * (tid & 31) : 16 * wave + 4 * kg, er = LDSE ? tid >> 5 : lc;
@@ -885,8 +880,7 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
         const int64_t m0 = tile * BM;
         const int rmax = (int)min((int64_t)(BM - 1), p.M - 1 - m0);
         const float* zb = p.Z + m0 * p.ldz;
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
+        const int ln = opaque(lane);
         const int idx = (wave * NI + i) * 64 + ln;
         const int r = idx / CH, pos = idx - r * CH;
         const int k = 4 * (pos ^ r);
@@ -900,19 +894,14 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     };
     // gate inputs of a tile (wave 0): piece 0 = C_in | C_out | C_dir | C_und (16 lanes each), piece 1 = C_all
     auto issue_G = [&](int64_t tile, int slot) {
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
+        const int ln = opaque(lane);
         const int64_t r = p.gate_mode == PG_GATES_SCALAR ? 0 : min(tile * BM + (ln & 15), p.M - 1);
-        const float* c0 = p.C_in;
-        const float* c1 = p.C_out;
-        const float* c2 = p.C_dir;
-        const float* c3 = p.C_und;
-        const float* c4 = p.C_all;
-        asm volatile("" : "+s"(c0), "+s"(c1), "+s"(c2), "+s"(c3), "+s"(c4));
+        const float* c[5];
+        gate_ptrs(p, c);
         const int q = ln >> 4;
-        const float* cq = q == 0 ? c0 : q == 1 ? c1 : q == 2 ? c2 : c3;
+        const float* cq = q == 0 ? c[0] : q == 1 ? c[1] : q == 2 ? c[2] : c[3];
         glds4(cq + r, &Gi[slot][0][0]);
-        glds4(c4 + r, &Gi[slot][4][0]);
+        glds4(c[4] + r, &Gi[slot][4][0]);
     };
     // constant and residual of this lane's epilogue float4 (row er, columns ec) of a tile: two global_load_dwordx4,
     // issued at the top of the tile's own iteration and first used after its MFMAs. Always two loads per wave (an
@@ -923,13 +912,8 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     [[maybe_unused]] f32x4 cv = {0.f, 0.f, 0.f, 0.f}, rv = cv;
     [[maybe_unused]] auto load_CR = [&](int64_t tile) {
         if (DEXP(4)) return;
-        const int64_t m0 = tile * BM;
-        const int rmax = (int)min((int64_t)(BM - 1), p.M - 1 - m0);
-        const int rr = min(er, rmax);
-        const float* cb = has_const ? p.constant + m0 * p.ld_const + (rr * (int)p.ld_const) : p.Z + m0 * p.ldz;
-        const float* rb = !id_res    ? p.Z + m0 * p.ldz
-                          : p.map_res ? p.res_x + ngram_row(p, m0 + rr) * p.ld_res
-                                      : p.res_x + m0 * p.ld_res + (rr * (int)p.ld_res);
+        const float *cb, *rb;
+        cr_rows<true, BM>(p, has_const, id_res, tile, er, cb, rb);
         if (p.nt_a)
             asm volatile("global_load_dwordx4 %0, %2, off nt\n\tglobal_load_dwordx4 %1, %3, off"
                          : "=&v"(cv), "=&v"(rv)
@@ -948,26 +932,12 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     };
     [[maybe_unused]] auto issue_CR = [&](int64_t tile) {  // LDSE: wave w fetches rows 2w, 2w + 1 into Cs / Rs
         if (DEXP(4)) return;
-        const int64_t m0 = tile * BM;
-        const int rmax = (int)min((int64_t)(BM - 1), p.M - 1 - m0);
-        int ln = lane;
-        asm volatile("" : "+v"(ln));
-        const int rr = min(2 * wave + (ln >> 5), rmax);
-        const float* cb = has_const ? p.constant + m0 * p.ld_const + (rr * (int)p.ld_const) : p.Z + m0 * p.ldz;
-        const float* rb = !id_res    ? p.Z + m0 * p.ldz
-                          : p.map_res ? p.res_x + ngram_row(p, m0 + rr) * p.ld_res
-                                      : p.res_x + m0 * p.ld_res + (rr * (int)p.ld_res);
+        const int ln = opaque(lane);
+        const float *cb, *rb;
+        cr_rows<true, BM>(p, has_const, id_res, tile, 2 * wave + (ln >> 5), cb, rb);
         if (p.nt_a) glds16nt(cb + 4 * (ln & 31), Cs + wave * 256);
         else glds16(cb + 4 * (ln & 31), Cs + wave * 256);
         glds16(rb + 4 * (ln & 31), Rs + wave * 256);
-    };
-    auto gates = [&](int slot, int r, float& s0, float& s1, float& s2) {
-        float c[5];
-        lds_gates5<BM * 4>(&Gi[slot][0][r], c);
-        const float cad = c[4] * c[2];
-        s0 = cad * c[0];
-        s1 = cad * c[1];
-        s2 = c[4] * c[3];
     };
     // fp32 tile -> three bf16 images; thread j converts units j and j + 512 (row j & 15, unit j >> 4): waves 0-3
     // two units, waves 4-7 one; all of a thread's fp32 reads in one LDS round trip
@@ -981,8 +951,11 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
         if (two) lds_ld4x4(&Af[r * K + 4 * (c00 ^ r)], &Af[r * K + 4 * ((c00 + 4) ^ r)], &Af[r * K + 4 * (c10 ^ r)],
                            &Af[r * K + 4 * ((c10 + 4) ^ r)], x);
         else lds_ld4x2(&Af[r * K + 4 * (c00 ^ r)], &Af[r * K + 4 * ((c00 + 4) ^ r)], x[0], x[1]);
-        float sg[3] = {1.f, 1.f, 1.f};
-        if (!PRE) gates(gslot, r, sg[0], sg[1], sg[2]);
+        float sg[3] = {1.f, 1.f, 1.f}, gc[5];
+        if (!PRE) {
+            lds_gates5<BM * 4>(&Gi[gslot][0][r], gc);
+            gate_scales(gc, sg[0], sg[1], sg[2]);
+        }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (i == 1 && !two) break;
@@ -1070,8 +1043,8 @@ __global__ __launch_bounds__(512) void dense_x3p_kernel(DenseP p) {
     auto epilogue = [&](int64_t m0, float4 ov, float4 cq, float4 rq, const float (&c)[5]) {
         if (!has_const) cq = make_float4(0.f, 0.f, 0.f, 0.f);
         if (!id_res) rq = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float cad = c[4] * c[2];
-        const float s0 = cad * c[0], s1 = cad * c[1], s2 = c[4] * c[3];
+        float s0, s1, s2;
+        gate_scales(c, s0, s1, s2);
         const float o[4] = {ov.x, ov.y, ov.z, ov.w}, C4[4] = {cq.x, cq.y, cq.z, cq.w}, R4[4] = {rq.x, rq.y, rq.z, rq.w};
         const float B0[4] = {bq[0].x, bq[0].y, bq[0].z, bq[0].w}, B1[4] = {bq[1].x, bq[1].y, bq[1].z, bq[1].w},
                     B2[4] = {bq[2].x, bq[2].y, bq[2].z, bq[2].w}, BR[4] = {bq[3].x, bq[3].y, bq[3].z, bq[3].w};

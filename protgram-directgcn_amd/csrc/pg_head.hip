@@ -39,7 +39,7 @@ struct HeadP {
     int64_t lde;
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using pg::ld4;
 
 template <int FMAX, int HMAX, int CMAX>
 __global__ __launch_bounds__(256) void head_kernel(HeadP p) {

@@ -36,6 +36,7 @@
 
 #include "pg_bf16_util.h"
 #include "pg_common.h"
+#include "pg_lds.h"
 
 namespace {
 
@@ -117,17 +118,12 @@ constexpr int XSTAMP_CH = 32, XSTAMP_PT = 8, XSTAMP_LAST = XSTAMP_CH - 1;  // ch
     } while (0)
 #endif
 
-// Hide a per-lane LDS offset from the optimiser: the per-tile compile-time parts then stay ds_read/ds_write
-// immediate offsets (< 64 KiB) instead of being folded with the region base into one constant per tile, each
-// needing its own register.
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-__device__ __forceinline__ void glds16(const void* src, const void* lds_base) {
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
+// pg_lds.h; opaque() hides per-lane LDS offsets here (folded with the region bases, each tile's needed a register)
+using pg::glds16;
+using pg::glds16_asm;
+using pg::lds_addr;
+using pg::opaque;
+using pg::vm_wait;
 
 // Loader wave lw after issuing the next chunk's in-source pieces: wait until everything it issued before them (the
 // out / self / diagonal pieces) has landed, leaving its own in-source pieces (the youngest vector-memory operations;
@@ -625,36 +621,8 @@ constexpr int T2_TPW = 5;                              // tiles per wave per sub
 static_assert(T2_NIN * 1024 <= T2_SLOT && T2_NOUT * 1024 <= T2_SLOT && T2_NIN <= 32 && T2_NOUT <= 32, "ring slot");
 static_assert(4 * T2_SLOT + 2 * XR * 64 <= 163840, "LDS: four slots, P and the accumulate stage");
 
-// s_waitcnt vmcnt(min(n, 23)) for a wave-uniform n (a smaller bound than needed only waits longer)
-__device__ __forceinline__ void vm_wait(int n) {
-    switch (n < 0 ? 0 : n) {
-#define PG_VMW(k)                                              \
-    case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); \
-        break;
-        PG_VMW(0) PG_VMW(1) PG_VMW(2) PG_VMW(3) PG_VMW(4) PG_VMW(5) PG_VMW(6) PG_VMW(7) PG_VMW(8) PG_VMW(9)
-        PG_VMW(10) PG_VMW(11) PG_VMW(12) PG_VMW(13) PG_VMW(14) PG_VMW(15) PG_VMW(16) PG_VMW(17) PG_VMW(18)
-        PG_VMW(19) PG_VMW(20) PG_VMW(21) PG_VMW(22)
-#undef PG_VMW
-        default: asm volatile("s_waitcnt vmcnt(23)" ::: "memory"); break;
-    }
-}
-
 template <int V>
 using ic = std::integral_constant<int, V>;
-
-// LDS-DMA piece (16 B per lane -> LDS byte address lds + 16 lane) in inline asm: hidden from the compiler's wait
-// bookkeeping, which otherwise drains every DMA in flight (vmcnt(0)) before LDS reads it cannot tell apart from them
-// (at control-flow joins); the kernel counts these operations itself (vm_wait). M0 saved and restored in the statement.
-__device__ __forceinline__ void glds16_asm(const float* src, uint32_t lds) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds)
-                 : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(const float* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float*)p;
-}
 
 template <bool BF>
 __global__ __launch_bounds__(512) void ngram_midt2_kernel(XP p, int accumulate) {

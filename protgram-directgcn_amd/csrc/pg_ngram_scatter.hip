@@ -25,6 +25,7 @@
 // were loaded one chunk ahead. The out-direction workgroups also write D.
 #include "pg_bf16_util.h"
 #include "pg_common.h"
+#include "pg_lds.h"
 
 namespace {
 
@@ -60,18 +61,9 @@ struct SP {
 #define SEXP(bit) 0
 #endif
 
-// LDS-DMA of one 16-B piece per lane (global_load_lds_dwordx4: lane i's 16 B land at M0 + 16 i), as inline asm so
-// that the compiler's wait insertion does not see it (the builtin form makes it wait for every outstanding
-// vector-memory operation at control-flow joins); the kernel counts these operations itself. M0 saved and restored.
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src), "s"(lds)
-                 : "memory");
-}
+using pg::glds16_asm;  // the kernel's LDS-DMA pieces (pg_lds.h), counted by the kernel itself
 
-// s_waitcnt vmcnt(n) for a wave-uniform n in 0..24
+// s_waitcnt vmcnt(n) for the three values n takes here (0, 20, 24); not pg::vm_wait, which stops at vmcnt(23)
 __device__ __forceinline__ void vm_wait(int n) {
     switch (n) {
 #define PG_VMW(k)                                                  \
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(STHREADS) void ngram_scatter_kernel(SP p) {
         const uint32_t dst = lds0 + (uint32_t)((ch - ch0) & 1) * C::IMG + (uint32_t)wave * 1024;
 #pragma unroll
         for (int u = 0; u < NW; ++u)
-            if (u < nw) dma16(g + goff[u], dst + (uint32_t)(SWAVES * u) * 1024);
+            if (u < nw) glds16_asm(g + goff[u], dst + (uint32_t)(SWAVES * u) * 1024);
     };
     // out-direction D: items (row r, 4 features), weights of the item rows in registers
     constexpr int ND = (SR * 4 + STHREADS - 1) / STHREADS;

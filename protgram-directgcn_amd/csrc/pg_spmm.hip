@@ -61,7 +61,7 @@ __device__ __forceinline__ void row_gates(const GateIn& g, float s[3]) {
     s[2] = __fmul_rn(g.ca, g.cu);
 }
 
-__device__ __forceinline__ float fb(int v) { return __int_as_float(v); }
+using pg::fb;
 __device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
 

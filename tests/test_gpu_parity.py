@@ -427,7 +427,11 @@ def test_model_inference_path_vs_reference(pkg, cuda, name):
                                                       (2050, 128, 128, False, False, False), (700, 128, 128, True, True, False),
                                                       (1500, 64, 128, True, True, False), (17, 128, 128, False, True, False), (1, 128, 128, False, True, False),
                                                       (5, 128, 128, False, False, False),
-                                                      (8200, 128, 128, False, True, False), (4111, 128, 128, True, True, False)])
+                                                      (8200, 128, 128, False, True, False), (4111, 128, 128, True, True, False),
+                                                      # the 32-row kernel on a grid that is a multiple of 8 (the XCD
+                                                      # branch of its tile range): 8 tiles, one per workgroup; 514
+                                                      # tiles on 256 workgroups, the last tile of one row
+                                                      (256, 64, 128, True, True, False), (16417, 64, 128, True, True, False)])
 def test_dense_kernel_variants_vs_float64(pkg, cuda, M, Fin, Fout, proj, vec, rows):
     """pg_directgcn_dense_f32 (the split-bf16 W-stationary kernels where their shape applies -- flags 0 -- and the
     tiled fp32 kernel, PG_FLAG_DENSE_TILED; pre-gated operands) against the same formula in float64. Pre-gated: the

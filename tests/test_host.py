@@ -46,6 +46,23 @@ def test_dgrad_kernels_have_no_packed_fp32_ops():
     assert sum(head.values()) > 0, "the audit finds no packed-FP32 op anywhere: it would not catch one"
 
 
+def test_isa_diff_compares_whole_kernel_streams():
+    """tools/isa_diff.py (the refactors' parent / branch comparison): an object against itself is `same` kernel by
+    kernel with status 0; two different objects under --require-same give status 1 and per-class counts."""
+    import subprocess
+    import sys
+    build = os.path.join(REPO, "protgram-directgcn_amd", "build")
+    a, b = os.path.join(build, "pg_head.o"), os.path.join(build, "pg_labels.o")
+    if not (os.path.exists(a) and os.path.exists(b)):
+        pytest.skip("library objects not built here (run __graft_entry__.build())")
+    tool = [sys.executable, os.path.join(REPO, "tools", "isa_diff.py")]
+    r = subprocess.run(tool + [a, a, "--require-same", "."], capture_output=True, text=True)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0 and len(lines) >= 2 and all(": same (" in ln for ln in lines), r.stdout + r.stderr
+    r = subprocess.run(tool + [a, b, "--require-same", "."], capture_output=True, text=True)
+    assert r.returncode == 1 and "absent" in r.stdout and "v_mfma=" in r.stdout and "s_waitcnt=" in r.stdout, r.stdout
+
+
 def test_abi_argument_errors_without_gpu(pkg):
     lib = pkg.load_library()
     # argument validation happens before any HIP call

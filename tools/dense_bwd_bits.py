@@ -1,6 +1,7 @@
-"""Bit-identity probe of the dense backward between two builds of the library (a refactor's parent and its branch).
+"""Bit-identity probe of the dense backward (or, with --forward, the dense forward) between two builds of the library
+(a refactor's parent and its branch).
 
-    python tools/dense_bwd_bits.py PARENT_LIB BRANCH_LIB [--out FILE] [--dir DIR] [--timeout SECONDS]
+    python tools/dense_bwd_bits.py [--forward] PARENT_LIB BRANCH_LIB [--out FILE] [--dir DIR] [--timeout SECONDS]
 
 For each library one fresh child process (PG_DIRECTGCN_LIB set to it) runs the case list below on the seeded
 tests/test_gpu_parity._dense_case inputs, every case with dropout 0 and 0.3, and writes the bytes of every tensor
@@ -8,10 +9,16 @@ ops.layer_dense_backward / ops.gemm_at_b returns under DIR/<parent|branch>/. Thi
 the host (it never opens the GPU) and prints one `equal` / `DIFFERS` line per tensor and a count; exit status 0 only
 when every tensor is byte-equal. Each child has its own time limit; after a child that exits abnormally nothing more
 is started.
+
+--forward: ops.layer_dense and ops.layer_dense_ngram_rows instead (child_forward below): the pipelined split-bf16 kernel
+at FWD_X3P_M rows and the 32-row one (F_in 64 with W_res) at FWD_X3_M, both gate modes, constant / identity residual /
+pre-gated operand on and off, dropout 0 and 0.3, each under FWD_FLAGS; packed and unpacked weights; the n-gram row map.
+Outputs above 64 KiB are dumped as their SHA-256 and length.
 """
 from __future__ import annotations
 
 import argparse
+import hashlib
 import os
 import shutil
 import subprocess
@@ -55,6 +62,86 @@ CASES = [
     dict(name="bf16tiled_777x64to128_proj_rows", M=777, Fin=64, Fout=128, proj=True, rows=True, bf16=True),
     dict(name="bf16tiled_1000x128_flag", M=1000, Fin=128, Fout=128, bf16=True, flags=("PG_FLAG_WGRAD_BF16_TILED",)),
 ]
+
+
+# rows: 1 | one tile | + 1 row | 8 tiles (a grid that is a multiple of 8: XCD-contiguous tile ranges) | 9 tiles (not) |
+# 257 tiles on 256 workgroups, the last of 3 rows | 517 tiles; the 32-row kernel: 2 tiles | 8 | 514, the last of 1 row
+FWD_X3P_M = (1, 16, 17, 128, 144, 4099, 8272)
+FWD_X3_M = (33, 256, 16417)
+FWD_FLAGS = (None, "PG_FLAG_DENSE_LDS_EPILOGUE", "PG_FLAG_DENSE_NO_IL", "PG_FLAG_DENSE_A_CACHED", "PG_FLAG_DENSE_TILED")
+
+
+def child_forward(outdir: str) -> int:
+    import ctypes
+    import itertools
+
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import torch
+    from __graft_entry__ import load_package
+    load_package()
+    from protgram_directgcn_amd import _lib, ops
+    from test_gpu_parity import _dense_case
+
+    dev = torch.device("cuda:0")
+    os.makedirs(outdir, exist_ok=True)
+    lib = ops.load_library()
+
+    def save(name, t):
+        b = t.detach().contiguous().cpu().view(torch.uint8).numpy().tobytes()
+        if len(b) > 65536:
+            b = f"sha256 {hashlib.sha256(b).hexdigest()} of {len(b)} bytes\n".encode()
+        with open(os.path.join(outdir, name + ".bin"), "wb") as f:
+            f.write(b)
+
+    def gated(Z, prm, Fin):  # s_q * Z_q with fp32 gates: the operand PG_FLAG_DENSE_PREGATED expects
+        ca, cd = prm["C_all"], prm["C_directed"]
+        s = (ca * cd * prm["C_in"], ca * cd * prm["C_out"], ca * prm["C_undirected"])
+        return torch.cat([Z[:, k * Fin:(k + 1) * Fin] * s[k][:Z.size(0)] for k in range(3)], 1)
+
+    for Fin, proj, Ms in ((128, False, FWD_X3P_M), (64, True, FWD_X3_M)):
+        for M, vec in itertools.product(Ms, (True, False)):
+            Z, xres, prm, const, _, W_res, b_res, _ = _dense_case(M, Fin, 128, proj, vec, False, 7 * M + Fin)
+            Zs = {False: Z.to(dev), True: gated(Z, prm, Fin).to(dev)}
+            prm = {k: v.to(dev) for k, v in prm.items()}
+            xg, cg = xres.to(dev), const.to(dev) if vec else None
+            Wr, br = (W_res.to(dev), b_res.to(dev)) if proj else (None, None)
+            seed = torch.tensor([0x0123_4567_89AB_CDEF + M], dtype=torch.int64, device=dev)
+            for uc, ur, pre, drop in itertools.product((True, False) if vec else (False,), (True,) if proj else (True, False),
+                                                       (False, True), DROPS):
+                tag = f"fwd_{M}x{Fin}_{'vec' if vec else 'scalar'}_c{int(uc)}r{int(ur)}p{int(pre)}.drop{drop}"
+                kw = dict(constant=cg if uc else None, res_x=xg if ur else None, W_res=Wr, b_res=br, act=True,
+                          pregated=pre, drop=(drop, seed) if drop else None)
+                for f in FWD_FLAGS:
+                    fl = ops.default_flags() | (getattr(_lib, f) if f else 0)
+                    save(f"{tag}.{f or 'default'}", ops.layer_dense(Zs[pre], prm, 0 if vec else 1, flags=fl, **kw))
+                if not proj:  # packed weights (ops.layer_dense hands this kernel the unpacked ones)
+                    Y = torch.empty(M, 128, device=dev)
+                    a, keep = ops._layer_args(Zs[pre], prm, 0 if vec else 1, None, kw["constant"], kw["res_x"], None, True,
+                                              drop=kw["drop"])
+                    a.Y, a.ldy = ops._p(Y), Y.stride(0)
+                    packed = ops.pack_weights(prm, None, None)
+                    fl = ops.default_flags() | (_lib.PG_FLAG_DENSE_PREGATED if pre else 0)
+                    ops.check(lib.pg_directgcn_dense_f32(ctypes.byref(a), ops._p(packed), fl, ops._stream(Y)), "dense")
+                    torch.cuda.synchronize()
+                    del keep
+                    save(f"{tag}.packed", Y)
+    # n-gram row map: two middles (3 and 4) of a K = 20, Kn1 = 400 grid; residual read / output written at global rows
+    M, Kn1, m0 = 800, 400, 3
+    Z, xres, prm, const, _, _, _, _ = _dense_case(M, 128, 128, False, True, False, 7 * M + 128)
+    prm = {k: v.to(dev) for k, v in prm.items()}
+    xglob = torch.randn(20 * Kn1, 128, generator=torch.Generator().manual_seed(M)).to(dev)
+    for map_res, map_out in ((True, True), (True, False), (False, True)):
+        out = torch.zeros(20 * Kn1, 128, device=dev) if map_out else None
+        Y = ops.layer_dense_ngram_rows(Z.to(dev), prm, 0, Kn1, m0, constant=const.to(dev),
+                                       res_x=xglob if map_res else xres.to(dev), map_res=map_res, out=out,
+                                       map_out=map_out, act=True)
+        if Y is None:
+            print("fwd_ngram_rows: the entry point does not take this case", file=sys.stderr)
+            return 2
+        save(f"fwd_ngram_rows_res{int(map_res)}out{int(map_out)}", Y)
+    torch.cuda.synchronize()
+    return 0
 
 
 def child(outdir: str) -> int:
@@ -123,10 +210,11 @@ def main() -> int:
     ap.add_argument("--out", help="also write the report to this file")
     ap.add_argument("--dir", default=os.path.join(tempfile.gettempdir(), "dense_bwd_bits"), help="tensor dumps")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
+    ap.add_argument("--forward", action="store_true", help="the dense forward instead (child_forward)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        return child(a.child)
+        return child_forward(a.child) if a.forward else child(a.child)
     dirs = {}
     for tag, lib in (("parent", a.parent_lib), ("branch", a.branch_lib)):
         dirs[tag] = os.path.join(a.dir, tag)
@@ -134,8 +222,8 @@ def main() -> int:
         env = dict(os.environ, PG_DIRECTGCN_LIB=os.path.abspath(lib))
         env.pop("PG_SPMM_FLAGS", None)
         try:
-            rc = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--child", dirs[tag]], env=env,
-                                timeout=a.timeout).returncode
+            rc = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--child", dirs[tag]] +
+                                (["--forward"] if a.forward else []), env=env, timeout=a.timeout).returncode
         except subprocess.TimeoutExpired:
             rc = 124
         if rc != 0:
@@ -155,7 +243,8 @@ def main() -> int:
             verdict += f"  {len(da)} bytes"
         bad += not verdict.startswith("equal")
         lines.append(f"{n[:-4]:60s} {verdict}")
-    lines.append(f"{len(names)} tensors of {len(CASES)} cases (dropout {DROPS[0]} and {DROPS[1]}): "
+    what = "the forward cases" if a.forward else f"{len(CASES)} cases"
+    lines.append(f"{len(names)} tensors of {what} (dropout {DROPS[0]} and {DROPS[1]}): "
                  f"{len(names) - bad} equal, {bad} DIFFERS")
     report = "\n".join(lines)
     print(report)

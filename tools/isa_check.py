@@ -15,7 +15,16 @@ import subprocess
 import sys
 import tempfile
 
-LLVM = "/opt/rocm/lib/llvm/bin"
+def llvm_dir() -> str:
+    """The LLVM tools next to the compiler: $ROCM_PATH, else the ROCm of $HIPCC (<rocm>/bin/hipcc), else /opt/rocm."""
+    hipcc = os.environ.get("HIPCC", "")
+    rocm = os.environ.get("ROCM_PATH") or (os.path.dirname(os.path.dirname(os.path.abspath(hipcc)))
+                                           if os.path.dirname(hipcc) else "/opt/rocm")
+    d = os.path.join(rocm, "lib", "llvm", "bin")
+    return d if os.path.isdir(d) else "/opt/rocm/lib/llvm/bin"
+
+
+LLVM = llvm_dir()
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 PACKED_FP32 = ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32")
 
