@@ -7,14 +7,19 @@
 // (v_mfma_f32_32x32x2_f32, B operands straight from the L1/L2-resident weights), and finishes the row
 // softmax in LDS. Replaces 6+ framework launches and two re-reads of h.
 // Fast path: F <= 256, H <= 128, C <= 64 (F, H multiples of 4); other shapes use a one-wave-per-row
-// fallback kernel. The model's own shape (F = 128 -> 64 -> C <= 32) runs head_x3_kernel (split-bf16 decoder 1;
-// head_f128_kernel, its fp32-MFMA predecessor, with -DPG_HEAD_FP32). A persistent form of head_x3_kernel (W1 splits
+// fallback kernel. The model's own shape (F = 128 -> 64 -> C <= 32) runs head_x3_kernel (split-bf16 decoder 1). Its
+// predecessor head_f128_kernel (the same tiling with decoder 1 on v_mfma_f32_16x16x4_f32 from an fp32 h tile in LDS)
+// measured 0.0615 ms per launch against 0.053 ms and is gone. A persistent form of head_x3_kernel (W1 splits
 // and W2 kept in registers across a block's 32-row tiles, next tile's rows loaded behind the math; 128 VGPRs, four
 // blocks per CU) measured 0.062 ms against 0.050 for one tile per block; two 32-row tiles per block (W1 splits loaded
 // once per block; 128 VGPRs, occupancy 4) made the bench step 0.547 -> 0.580 ms (round 3). Round 4: unconditional W2
 // loads (no per-lane branch join, whose vmcnt(0) waited on the h rows an HBM round trip early) 47.6 -> 45.8 us per
 // launch (bench HIP events, two runs); W1 loaded first with its split pinned ahead of the h rows' arrival measured
 // 47.5 us (112 VGPRs, occupancy 4; forcing 5 spills), so the split stays where the compiler puts it.
+// The stages the kernels share are functions: decoder_tiles (head_kernel's two products) and row_log_softmax
+// (head_kernel, head_x3_kernel). The row load (fp32, or bf16 widened exactly) stays written out in both kernels: as a
+// function it moved head_x3_kernel's register counts (profiles/head_dedup_resource_usage.txt).
+#include "pg_bf16_util.h"
 #include "pg_common.h"
 #include "pg_split3.h"
 
@@ -41,6 +46,68 @@ struct HeadP {
 
 using pg::ld4;
 
+// D = A W^T + b (RELU: its positive part) for a 64-row tile: 2 x (N/32) tiles of 32x32 over the block's four waves,
+// K <= KMAX. A [64][lda] from LDS, B (= W rows, [N][K]) from the L2-resident weights, 4 k at a time with the K
+// permutation of pg_dense.hip. Columns j < ncol of D [64][ldd] are written, those at N and beyond as zeros.
+template <int KMAX, bool RELU>
+__device__ __forceinline__ void decoder_tiles(int K, int N, const float* A, int lda, const float* W, const float* bias,
+                                              float* D, int ldd, int ncol) {
+    const int wave = threadIdx.x >> 6, li = threadIdx.x & 31, lh = (threadIdx.x & 63) >> 5;
+    const int ntile_n = (N + 31) / 32;
+    for (int tile = wave; tile < 2 * ntile_n; tile += 4) {
+        const int tm = tile / ntile_n, tn = tile % ntile_n;
+        const int j = tn * 32 + li;
+        const bool jok = j < N;
+        const float* wrow = W + (int64_t)(jok ? j : 0) * K;
+        constexpr int KG = KMAX / 8;
+        float4 bf[KG];
+#pragma unroll
+        for (int g = 0; g < KG; ++g) {
+            const int k = g * 8 + 4 * lh;
+            bf[g] = (jok && k < K) ? ld4(wrow + k) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int g = 0; g < KG; ++g) {
+            const int k = g * 8 + 4 * lh;
+            const float4 a = k < K ? ld4(&A[(tm * 32 + li) * lda + k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 b = bf[g];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+        }
+        const float bj = jok ? bias[j] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            float v = acc[r] + bj;
+            if (RELU) v = v > 0.f ? v : 0.f;
+            if (j < ncol) D[row * ldd + j] = jok ? v : 0.f;
+        }
+    }
+}
+
+// log_softmax of one row of logits in LDS (max-shifted, as torch) on LANES adjacent lanes (lane t: classes t,
+// t + LANES, ..); row m of logp is written when m < M
+template <int LANES>
+__device__ __forceinline__ void row_log_softmax(const float* ls, int C, int64_t m, float* logp, int64_t ldp, int64_t M) {
+    const int t = threadIdx.x & (LANES - 1);
+    float mx = -INFINITY;
+    for (int c = t; c < C; c += LANES) mx = fmaxf(mx, ls[c]);
+#pragma unroll
+    for (int o = 1; o < LANES; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, LANES));
+    float se = 0.f;
+    for (int c = t; c < C; c += LANES) se += expf(ls[c] - mx);
+#pragma unroll
+    for (int o = 1; o < LANES; o <<= 1) se += __shfl_xor(se, o, LANES);
+    const float lse = mx + logf(se);
+    if (m < M)
+        for (int c = t; c < C; c += LANES) logp[m * ldp + c] = ls[c] - lse;
+}
+
 template <int FMAX, int HMAX, int CMAX>
 __global__ __launch_bounds__(256) void head_kernel(HeadP p) {
     constexpr int HLD = FMAX + 4, ZLD = HMAX + 4, LLD = CMAX + 1;
@@ -50,7 +117,6 @@ __global__ __launch_bounds__(256) void head_kernel(HeadP p) {
     __shared__ __attribute__((aligned(16))) float Zs[HB * ZLD];
     float* Ls = Hs;  // logits reuse the h tile once both decoder products are done
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int li = lane & 31, lh = lane >> 5;
     const int F4 = p.F >> 2;
     const int64_t ntiles = (p.M + HB - 1) / HB;
 
@@ -63,16 +129,12 @@ __global__ __launch_bounds__(256) void head_kernel(HeadP p) {
             const int idx = tid + 256 * q;
             const int r = idx / (FMAX / 4), c4 = idx % (FMAX / 4);
             const int64_t m = t * HB + r;
-            if (m < p.M && c4 < F4) {
-                if (p.hb) {
-                    const uint2 w = *reinterpret_cast<const uint2*>(p.hb + m * p.ldh + 4 * c4);
-                    hv[q] = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u),
-                                        __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
-                } else {
-                    hv[q] = ld4(p.h + m * p.ldh + 4 * c4);
-                }
-            } else {
+            if (m >= p.M || c4 >= F4) {
                 hv[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else if (p.hb) {  // bf16 mode: widened exactly
+                hv[q] = pgbf::unpack4(*reinterpret_cast<const uint2*>(p.hb + m * p.ldh + 4 * c4));
+            } else {
+                hv[q] = ld4(p.h + m * p.ldh + 4 * c4);
             }
         }
     };
@@ -113,240 +175,31 @@ __global__ __launch_bounds__(256) void head_kernel(HeadP p) {
             }
         }
 
-        // 3. z = relu(h W1^T + b1): (HB/32) x (H/32) tiles of 32x32, K = F. A from LDS, B (= W1 rows)
-        //    from the L2-resident weights, 4 k at a time with the K permutation of pg_dense.hip.
-        {
-            const int ntile_n = (p.H + 31) / 32;
-            for (int tile = wave; tile < 2 * ntile_n; tile += 4) {
-                const int tm = tile / ntile_n, tn = tile % ntile_n;
-                const int j = tn * 32 + li;
-                const bool jok = j < p.H;
-                const float* w1row = p.W1 + (int64_t)(jok ? j : 0) * p.F;
-                constexpr int KG = FMAX / 8;
-                float4 bf[KG];
-#pragma unroll
-                for (int g = 0; g < KG; ++g) {
-                    const int k = g * 8 + 4 * lh;
-                    bf[g] = (jok && k < p.F) ? ld4(w1row + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int g = 0; g < KG; ++g) {
-                    const int k = g * 8 + 4 * lh;
-                    const float4 a = k < p.F ? ld4(&Hs[(tm * 32 + li) * HLD + k]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float4 b = bf[g];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-                }
-                const float bj = jok ? p.b1[j] : 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    const float z = acc[r] + bj;
-                    if (j < ZLD - 4) Zs[row * ZLD + j] = jok ? (z > 0.f ? z : 0.f) : 0.f;
-                }
-            }
-        }
+        // 3. z = relu(h W1^T + b1), K = F; the padded hidden columns (H <= j < HMAX) are written as zeros
+        decoder_tiles<FMAX, true>(p.F, p.H, Hs, HLD, p.W1, p.b1, Zs, ZLD, ZLD - 4);
         __syncthreads();  // Zs complete; Hs free (-> Ls)
 
-        // 4. logits = z W2^T + b2: (HB/32) x (C/32) tiles, K = H
-        {
-            const int ntile_n = (p.C + 31) / 32;
-            for (int tile = wave; tile < 2 * ntile_n; tile += 4) {
-                const int tm = tile / ntile_n, tn = tile % ntile_n;
-                const int c = tn * 32 + li;
-                const bool cok = c < p.C;
-                const float* w2row = p.W2 + (int64_t)(cok ? c : 0) * p.H;
-                constexpr int KG = HMAX / 8;
-                float4 bf[KG];
-#pragma unroll
-                for (int g = 0; g < KG; ++g) {
-                    const int k = g * 8 + 4 * lh;
-                    bf[g] = (cok && k < p.H) ? ld4(w2row + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-                for (int g = 0; g < KG; ++g) {
-                    const int k = g * 8 + 4 * lh;
-                    const float4 a = k < p.H ? ld4(&Zs[(tm * 32 + li) * ZLD + k]) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    const float4 b = bf[g];
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-                }
-                const float bc = cok ? p.b2[c] : 0.f;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    if (cok) Ls[row * LLD + c] = acc[r] + bc;
-                }
-            }
-        }
+        // 4. logits = z W2^T + b2, K = H
+        decoder_tiles<HMAX, false>(p.H, p.C, Zs, ZLD, p.W2, p.b2, Ls, LLD, p.C);
         __syncthreads();
 
-        // 5. log_softmax per row (max-shifted, as torch): 4 lanes per row
-        {
-            const int r = tid >> 2, tt = tid & 3;
-            const int64_t m = m0 + r;
-            float mx = -INFINITY;
-            for (int c = tt; c < p.C; c += 4) mx = fmaxf(mx, Ls[r * LLD + c]);
-            mx = fmaxf(mx, __shfl_xor(mx, 1, 4));
-            mx = fmaxf(mx, __shfl_xor(mx, 2, 4));
-            float se = 0.f;
-            for (int c = tt; c < p.C; c += 4) se += expf(Ls[r * LLD + c] - mx);
-            se += __shfl_xor(se, 1, 4);
-            se += __shfl_xor(se, 2, 4);
-            const float lse = mx + logf(se);
-            if (m < p.M)
-                for (int c = tt; c < p.C; c += 4) p.logp[m * p.ldp + c] = Ls[r * LLD + c] - lse;
-        }
+        // 5. log_softmax per row: 4 lanes per row
+        row_log_softmax<4>(&Ls[(tid >> 2) * LLD], p.C, m0 + (tid >> 2), p.logp, p.ldp, p.M);
         __syncthreads();  // Ls (= Hs) is read before the next tile is staged
     }
 }
 
 // The model's own head shape (F = 128 -> H = 64 -> C <= 32; ProtGramDirectGCN's decoder is F -> F/2 -> C):
-// one 32-row tile per 256-thread block, no persistent loop, small enough (LDS 30 KB, <= 128 VGPRs) for four
-// blocks per CU, so one block's loads, MFMAs and softmax overlap the others'. Decoder products on
-// v_mfma_f32_16x16x4f32 with a K permutation (lane (i, q) supplies k = 4q + 16m + t for t = 0..3 as four
-// consecutive MFMAs, the weights in the same order); both weight fragments stay in registers for the block.
-// Rows of the LDS tiles are padded by 8 floats: the (row, 4q) float4 reads of one ds_read_b128 lane group hit 16
-// distinct 16-B bank slots.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void head_f128_kernel(HeadP p) {
-    constexpr int BM = 32, F = 128, H = 64, CP = 32;
-    constexpr int HLD = F + 8, ZLD = H + 8, LLD = CP + 1;
-    __shared__ __attribute__((aligned(16))) float Hs[BM * HLD];
-    __shared__ __attribute__((aligned(16))) float Zs[BM * ZLD];
-    __shared__ __attribute__((aligned(16))) float Ls[BM * LLD];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int li = lane & 15, q = lane >> 4;
-    const int64_t m0 = (int64_t)blockIdx.x * BM;
-    // 1. h tile (4 float4 per thread, 512-B rows), then the weight fragments while the loads are in flight
-    float4 hv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int r = (tid >> 5) + 8 * k;
-        const int64_t m = m0 + r;
-        if (m >= p.M) {
-            hv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        } else if (p.hb) {  // bf16 mode: widened exactly
-            const uint2 w = *reinterpret_cast<const uint2*>(p.hb + m * p.ldh + 4 * (tid & 31));
-            hv[k] = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u),
-                                __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
-        } else {
-            hv[k] = ld4(p.h + m * p.ldh + 4 * (tid & 31));
-        }
-    }
-    float4 w1f[8], w2f[4];
-    {
-        const float* w1row = p.W1 + (int64_t)(16 * wave + li) * F + 4 * q;  // decoder 1: wave w owns hidden 16w..16w+15
-#pragma unroll
-        for (int m = 0; m < 8; ++m) w1f[m] = ld4(w1row + 16 * m);
-        const int c = 16 * (wave >> 1) + li;  // decoder 2: row block wave & 1, classes 16 (wave >> 1) + li
-        const bool cok = c < p.C;
-        const float* w2row = p.W2 + (int64_t)(cok ? c : 0) * H + 4 * q;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) w2f[m] = cok ? ld4(w2row + 16 * m) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float b1v = p.b1[16 * wave + li];
-    const int c2 = 16 * (wave >> 1) + li;
-    const float b2v = c2 < p.C ? p.b2[c2] : 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(&Hs[((tid >> 5) + 8 * k) * HLD + 4 * (tid & 31)]) = hv[k];
-    __syncthreads();
-    // 2. embeddings: 8 threads per row, 16 columns each
-    {
-        const int r = tid >> 3, part = tid & 7;
-        float4 v[4];
-        float ss = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[k] = ld4(&Hs[r * HLD + 16 * part + 4 * k]);
-            ss += v[k].x * v[k].x + v[k].y * v[k].y + v[k].z * v[k].z + v[k].w * v[k].w;
-        }
-        ss += __shfl_xor(ss, 1, 8);
-        ss += __shfl_xor(ss, 2, 8);
-        ss += __shfl_xor(ss, 4, 8);
-        const int64_t m = m0 + r;
-        if (m < p.M) {
-            const float inv = 1.0f / (sqrtf(ss) + p.eps);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                *reinterpret_cast<float4*>(p.emb + m * p.lde + 16 * part + 4 * k) =
-                    make_float4(v[k].x * inv, v[k].y * inv, v[k].z * inv, v[k].w * inv);
-        }
-    }
-    // 3. z = relu(h W1^T + b1): wave w computes hidden columns 16w..16w+15 for both 16-row blocks
-    {
-        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                const float4 a = ld4(&Hs[(16 * rb + li) * HLD + 4 * q + 16 * m]);
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w1f[m].x, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w1f[m].y, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w1f[m].z, acc[rb], 0, 0, 0);
-                acc[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w1f[m].w, acc[rb], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float z = acc[rb][i] + b1v;
-                Zs[(16 * rb + 4 * q + i) * ZLD + 16 * wave + li] = z > 0.f ? z : 0.f;
-            }
-    }
-    __syncthreads();
-    // 4. logits = z W2^T + b2: wave w -> rows 16 (w & 1).., classes 16 (w >> 1)..
-    {
-        const int rb = wave & 1;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const float4 a = ld4(&Zs[(16 * rb + li) * ZLD + 4 * q + 16 * m]);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w2f[m].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w2f[m].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w2f[m].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w2f[m].w, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) Ls[(16 * rb + 4 * q + i) * LLD + c2] = acc[i] + b2v;
-    }
-    __syncthreads();
-    // 5. log_softmax (max-shifted, as torch): 8 threads per row
-    {
-        const int r = tid >> 3, part = tid & 7;
-        const int64_t m = m0 + r;
-        float mx = -INFINITY;
-        for (int c = part; c < p.C; c += 8) mx = fmaxf(mx, Ls[r * LLD + c]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1, 8));
-        mx = fmaxf(mx, __shfl_xor(mx, 2, 8));
-        mx = fmaxf(mx, __shfl_xor(mx, 4, 8));
-        float se = 0.f;
-        for (int c = part; c < p.C; c += 8) se += expf(Ls[r * LLD + c] - mx);
-        se += __shfl_xor(se, 1, 8);
-        se += __shfl_xor(se, 2, 8);
-        se += __shfl_xor(se, 4, 8);
-        const float lse = mx + logf(se);
-        if (m < p.M)
-            for (int c = part; c < p.C; c += 8) p.logp[m * p.ldp + c] = Ls[r * LLD + c] - lse;
-    }
-}
-
-// Split-bf16 variant of head_f128_kernel (the default for its shape): decoder 1 (K = 128, 75 % of the head's
+// one 32-row tile per 256-thread block, no persistent loop, small enough (LDS 28 KB, <= 128 VGPRs) for four
+// blocks per CU, so one block's loads, MFMAs and softmax overlap the others'. Decoder 1 (K = 128, 75 % of the head's
 // matrix work) on v_mfma_f32_16x16x32_bf16 with exact three-way bf16 splits of h and W1 (pg_split3.h: six
 // products per k step, fp32-level accuracy) -- 48 bf16 MFMAs per wave instead of 64 fp32 16x16x4 ones at twice
 // the cycles each. The h tile never goes through LDS as fp32: each thread keeps its 4 rows x 4 columns in
 // registers, reduces the row norms across the row's 32 lanes, writes the embeddings, and stores its three bf16
-// splits (half a 16-B operand unit per row) into row-swizzled images. Decoder 2 and the softmax as head_f128.
+// splits (half a 16-B operand unit per row) into row-swizzled images. Decoder 2 on v_mfma_f32_16x16x4f32 with a K
+// permutation (lane (i, q) supplies k = 4q + 16m + t for t = 0..3 as four consecutive MFMAs, the weights in the same
+// order); both weight fragments stay in registers for the block. Rows of the z tile are padded by 8 floats: the
+// (row, 4q) float4 reads of one ds_read_b128 lane group hit 16 distinct 16-B bank slots.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) void head_x3_kernel(HeadP p) {
     constexpr int BM = 32, F = 128, H = 64, CP = 32;
     constexpr int ZLD = H + 8, LLD = CP + 1;
@@ -367,9 +220,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         if (m >= p.M) {
             hv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
         } else if (p.hb) {  // bf16 mode: widened exactly
-            const uint2 w = *reinterpret_cast<const uint2*>(p.hb + m * p.ldh + 4 * c4);
-            hv[k] = make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u),
-                                __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u));
+            hv[k] = pgbf::unpack4(*reinterpret_cast<const uint2*>(p.hb + m * p.ldh + 4 * c4));
         } else {
             hv[k] = ld4(p.h + m * p.ldh + 4 * c4);
         }
@@ -469,24 +320,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         for (int i = 0; i < 4; ++i) Ls[(16 * rb + 4 * q + i) * LLD + c2] = a[i] + b2v;
     }
     __syncthreads();
-    // 5. log_softmax (max-shifted, as torch): 8 threads per row
-    {
-        const int r = tid >> 3, part = tid & 7;
-        const int64_t m = m0 + r;
-        float mx = -INFINITY;
-        for (int c = part; c < p.C; c += 8) mx = fmaxf(mx, Ls[r * LLD + c]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1, 8));
-        mx = fmaxf(mx, __shfl_xor(mx, 2, 8));
-        mx = fmaxf(mx, __shfl_xor(mx, 4, 8));
-        float se = 0.f;
-        for (int c = part; c < p.C; c += 8) se += expf(Ls[r * LLD + c] - mx);
-        se += __shfl_xor(se, 1, 8);
-        se += __shfl_xor(se, 2, 8);
-        se += __shfl_xor(se, 4, 8);
-        const float lse = mx + logf(se);
-        if (m < p.M)
-            for (int c = part; c < p.C; c += 8) p.logp[m * p.ldp + c] = Ls[r * LLD + c] - lse;
-    }
+    // 5. log_softmax: 8 lanes per row
+    row_log_softmax<8>(&Ls[(tid >> 3) * LLD], p.C, m0 + (tid >> 3), p.logp, p.ldp, p.M);
 }
 
 // General shapes: one wave per row, VALU.
@@ -556,11 +391,7 @@ int head_launch(int64_t M, int64_t F, int64_t H, int64_t C, const float* h, cons
         return (unsigned)((ntiles + per_block - 1) / per_block);
     };
     if (vec && F == 128 && H == 64 && C <= 32 && ldh % 4 == 0 && lde % 4 == 0) {
-#ifdef PG_HEAD_FP32
-        hipLaunchKernelGGL(head_f128_kernel, dim3((unsigned)((M + 31) / 32)), dim3(256), 0, s, p);
-#else
         hipLaunchKernelGGL(head_x3_kernel, dim3((unsigned)((M + 31) / 32)), dim3(256), 0, s, p);
-#endif
     } else if (vec && F <= 128 && H <= 64 && C <= 32) {
         hipLaunchKernelGGL((head_kernel<128, 64, 32>), dim3(grid_of(2)), dim3(256), 0, s, p);
     } else if (vec && F <= 256 && H <= 128 && C <= 64) {

@@ -26,6 +26,9 @@
 // and backward phases, nothing stored); seed is a device int64 the caller draws from torch's generator per step.
 // Shapes: F = 128, H = 64, C <= 32 (the model's F = 128 head: hidden = final_dim / 2, protgram_directgcn.py:173-177);
 // others: PG_ERR_UNSUPPORTED, the caller runs the framework path.
+// head_train5_kernel below is the same step for the bf16 mode's F = 256 head. The two kernels share the layout of a
+// partial (Part), the loss tail (block_loss), the reduce kernel and, on the host, the argument checks with the
+// parameter fill (prepare) and the launch tail (launch); their shape and layout declines stay with each entry.
 #include <algorithm>
 #include <cmath>
 
@@ -37,23 +40,26 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TC = 32;  // classes, padded
 constexpr int NT = 512;
-// The tiling is written for F = 128 (H = 64, 64-row tiles, W1 staged in LDS) and F = 256 (H = 128, 32-row tiles, W1
-// read from the L2-resident weights); only F = 128 is launched (shape_ok). Row strides are 18 mod 32 floats: the
-// 16x16x4 operand reads (16 rows x 2 k per 32-lane half) fall on distinct banks.
-template <int F> struct HT {
-    static constexpr int H = F / 2, TR = F == 128 ? 64 : 32;
-    static constexpr bool W1L = F == 128;  // W1 in LDS
-    static constexpr int LDH = F + 18, LDW1 = F + 18, LDA = H + 18, LDW2 = H + 18, LDL = TC + 18;
-    static constexpr int HT4 = TR * F / 4 / NT;  // float4 of the h tile per thread
-    // per-workgroup partial: dW1 [H][F], db1 [H], dW2 [C][H], db2 [C], loss
+// per-workgroup partial of either kernel: dW1 [H][F], db1 [H], dW2 [TC][H], db2 [TC], loss
+template <int F> struct Part {
+    static constexpr int H = F / 2;
     static constexpr int P_DW1 = 0, P_DB1 = H * F, P_DW2 = P_DB1 + H, P_DB2 = P_DW2 + TC * H, P_LOSS = P_DB2 + TC;
     static constexpr int P_STRIDE = (P_LOSS + 1 + 3) / 4 * 4;
-    static constexpr int LDS_FLOATS = (W1L ? H * LDW1 : 0) + TC * LDW2 + TR * LDH + 2 * TR * LDA + TR * LDL;
-    // tiles of 16x16 per wave: A = TR x H, dW2 = 32 x H, da = TR x H, dh = TR x F, dW1 = H x F
-    static constexpr int QA = (TR / 16) * (H / 16) / 8, QW2 = 2 * (H / 16) / 8, QD = (TR / 16) * (H / 16) / 8;
-    static constexpr int QE = (TR / 16) * (F / 16) / 8, QW1 = (H / 16) * (F / 16) / 8;
-    static_assert(HT4 * NT * 4 == TR * F && QA >= 1 && QW2 >= 1 && QD >= 1 && QE >= 1 && QW1 >= 1, "tiling");
 };
+
+// head_train_kernel's tiling: F = 128, H = 64, 64-row tiles, W1 staged in LDS. Row strides are 18 mod 32 floats: the
+// 16x16x4 operand reads (16 rows x 2 k per 32-lane half) fall on distinct banks.
+namespace h3 {
+constexpr int F = 128, H = 64, TR = 64;
+constexpr int LDH = F + 18, LDW1 = F + 18, LDA = H + 18, LDW2 = H + 18, LDL = TC + 18;
+constexpr int HT4 = TR * F / 4 / NT;  // float4 of the h tile per thread
+using PT = Part<F>;
+constexpr int LDS_FLOATS = H * LDW1 + TC * LDW2 + TR * LDH + 2 * TR * LDA + TR * LDL;
+// tiles of 16x16 per wave: A = TR x H, dW2 = 32 x H, da = TR x H, dh = TR x F, dW1 = H x F
+constexpr int QA = (TR / 16) * (H / 16) / 8, QW2 = 2 * (H / 16) / 8, QD = (TR / 16) * (H / 16) / 8;
+constexpr int QE = (TR / 16) * (F / 16) / 8, QW1 = (H / 16) * (F / 16) / 8;
+static_assert(HT4 * NT * 4 == TR * F && QA >= 1 && QW2 >= 1 && QD >= 1 && QE >= 1 && QW1 >= 1, "tiling");
+}  // namespace h3
 
 struct HeadTrainP {
     int64_t M;
@@ -87,34 +93,47 @@ __device__ __forceinline__ uint32_t drop_hash(uint64_t seed, int64_t m, int j, i
     return (uint32_t)x;
 }
 
-template <int F>
+// the workgroup's loss into its partial: lanes in order within the wave, then waves in order
+__device__ __forceinline__ void block_loss(float lossp, float lw, float* out) {
+    __shared__ float red[NT / 64];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    float v = lossp;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+        for (int w = 0; w < NT / 64; ++w) s += red[w];
+        *out = s * lw;
+    }
+}
+
 __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
-    using T = HT<F>;
-    constexpr int H = T::H, TR = T::TR, LDH = T::LDH, LDW1 = T::LDW1, LDA = T::LDA, LDW2 = T::LDW2, LDL = T::LDL;
-    __shared__ float lds[T::LDS_FLOATS];
-    float* W1s = lds;                                   // W1 [H][F] (F = 128 only)
-    float* W2s = W1s + (T::W1L ? H * LDW1 : 0);         // W2 [C][H], rows >= C zero
+    using namespace h3;
+    __shared__ float lds[LDS_FLOATS];
+    float* W1s = lds;                                   // W1 [H][F]
+    float* W2s = W1s + H * LDW1;                        // W2 [C][H], rows >= C zero
     float* Hs = W2s + TC * LDW2;                        // the h tile
     float* As = Hs + TR * LDH;                          // a (after relu and dropout)
     float* Ds = As + TR * LDA;                          // da
     float* Ls = Ds + TR * LDA;                          // logits, then dl
-    __shared__ float red[NT / 64];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int l16 = lane & 15, kq = lane >> 4;
     const int64_t ntiles = (p.M + TR - 1) / TR;
     const uint64_t seed = p.drop_thr ? (uint64_t)p.seed[0] : 0;
     const float gscale = p.scale ? p.scale[0] : 1.f;
-    // W1[j][k] for a 16x16x4 operand: LDS image or the global (L2-resident) weights
-    auto w1 = [&](int j, int k) -> float { return T::W1L ? W1s[j * LDW1 + k] : p.W1[j * F + k]; };
+    // W1[j][k] for a 16x16x4 operand, from the LDS image. A by-reference lambda on purpose: with the read written out at
+    // its two uses the compiler unrolls the two weight staging loops below another way (6 more loads and LDS writes).
+    auto w1 = [&](int j, int k) -> float { return W1s[j * LDW1 + k]; };
 
-    if (T::W1L)
-        for (int i = tid; i < H * F; i += NT) W1s[(i / F) * LDW1 + i % F] = p.W1[i];
+    for (int i = tid; i < H * F; i += NT) W1s[(i / F) * LDW1 + i % F] = p.W1[i];
     for (int i = tid; i < TC * H; i += NT) W2s[(i / H) * LDW2 + i % H] = i / H < p.C ? p.W2[i] : 0.f;
 
-    float4 hv[T::HT4];
+    float4 hv[HT4];
     auto load = [&](int64_t t) {
 #pragma unroll
-        for (int q = 0; q < T::HT4; ++q) {
+        for (int q = 0; q < HT4; ++q) {
             const int idx = tid + NT * q, r = idx / (F / 4), c4 = idx % (F / 4);
             const int64_t m = t * TR + r;
             hv[q] = m < p.M ? *reinterpret_cast<const float4*>(p.h + m * p.ldh + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -122,7 +141,7 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
     };
     auto stash = [&]() {
 #pragma unroll
-        for (int q = 0; q < T::HT4; ++q) {
+        for (int q = 0; q < HT4; ++q) {
             const int idx = tid + NT * q, r = idx / (F / 4), c4 = idx % (F / 4);
             float* d = &Hs[r * LDH + 4 * c4];
             d[0] = hv[q].x;
@@ -134,11 +153,11 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
 
     // persistent accumulators: dW1 tiles wave + 8 q (q < QW1, of the (H/16) x (F/16) grid), dW2 tiles (q < QW2, of
     // 2 x (H/16)), the bias column sums (db1: threads 0..H-1, db2: threads 256..256+C-1) and the loss
-    f32x4 accW1[T::QW1], accW2[T::QW2];
+    f32x4 accW1[QW1], accW2[QW2];
 #pragma unroll
-    for (int q = 0; q < T::QW1; ++q) accW1[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < QW1; ++q) accW1[q] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int q = 0; q < T::QW2; ++q) accW2[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int q = 0; q < QW2; ++q) accW2[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     float dbias = 0.f, lossp = 0.f;
 
     int64_t t = blockIdx.x;
@@ -152,21 +171,21 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
         // A: a = dropout(relu(h W1^T + b1)); the wave's tiles share their column tile, chains interleaved
         {
             constexpr int CT = H / 16;
-            f32x4 acc[T::QA];
+            f32x4 acc[QA];
 #pragma unroll
-            for (int q = 0; q < T::QA; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < QA; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
             const int ct = wave % CT;
 #pragma unroll 4
             for (int k = 0; k < F; k += 4) {
                 const float b = w1(16 * ct + l16, k + kq);
 #pragma unroll
-                for (int q = 0; q < T::QA; ++q)
+                for (int q = 0; q < QA; ++q)
                     acc[q] = mfma16(Hs[(16 * ((wave + 8 * q) / CT) + l16) * LDH + k + kq], b, acc[q]);
             }
             const int j = 16 * ct + l16;
             const float bj = p.b1[j];
 #pragma unroll
-            for (int q = 0; q < T::QA; ++q)
+            for (int q = 0; q < QA; ++q)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = 16 * ((wave + 8 * q) / CT) + 4 * kq + r;
@@ -235,7 +254,7 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
 
         // D: dW2 += dl^T a (tiles wave + 8 q of 2 x (H/16)); da = (dl W2) * (a > 0) / (1 - p); db2 column sums
 #pragma unroll
-        for (int q = 0; q < T::QW2; ++q) {
+        for (int q = 0; q < QW2; ++q) {
             const int tt = wave + 8 * q, ct = tt / (H / 16), ht = tt % (H / 16);
 #pragma unroll 4
             for (int k = 0; k < TR; k += 4)
@@ -243,21 +262,21 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
         }
         {
             constexpr int CT = H / 16;
-            f32x4 acc[T::QD];
+            f32x4 acc[QD];
 #pragma unroll
-            for (int q = 0; q < T::QD; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < QD; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
             const int ht = wave % CT;
 #pragma unroll
             for (int k = 0; k < TC; k += 4) {
                 const float b = W2s[(k + kq) * LDW2 + 16 * ht + l16];
 #pragma unroll
-                for (int q = 0; q < T::QD; ++q)
+                for (int q = 0; q < QD; ++q)
                     acc[q] = mfma16(Ls[(16 * ((wave + 8 * q) / CT) + l16) * LDL + k + kq], b, acc[q]);
             }
             const int j = 16 * ht + l16;
             const float ik = p.drop_thr ? p.inv_keep : 1.f;
 #pragma unroll
-            for (int q = 0; q < T::QD; ++q)
+            for (int q = 0; q < QD; ++q)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = 16 * ((wave + 8 * q) / CT) + 4 * kq + r;
@@ -275,19 +294,19 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
         // (H/16) x (F/16)); db1 column sums
         {
             constexpr int FT = F / 16;
-            f32x4 acc[T::QE];
+            f32x4 acc[QE];
 #pragma unroll
-            for (int q = 0; q < T::QE; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int q = 0; q < QE; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll 2
             for (int k = 0; k < H; k += 4) {
 #pragma unroll
-                for (int q = 0; q < T::QE; ++q) {
+                for (int q = 0; q < QE; ++q) {
                     const int tt = wave + 8 * q;
                     acc[q] = mfma16(Ds[(16 * (tt / FT) + l16) * LDA + k + kq], w1(k + kq, 16 * (tt % FT) + l16), acc[q]);
                 }
             }
 #pragma unroll
-            for (int q = 0; q < T::QE; ++q) {
+            for (int q = 0; q < QE; ++q) {
                 const int tt = wave + 8 * q, f = 16 * (tt % FT) + l16;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -298,7 +317,7 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
 #pragma unroll 1
             for (int k = 0; k < TR; k += 4) {
 #pragma unroll
-                for (int q = 0; q < T::QW1; ++q) {
+                for (int q = 0; q < QW1; ++q) {
                     const int tt = wave + 8 * q;
                     accW1[q] = mfma16(Ds[(k + kq) * LDA + 16 * (tt / FT) + l16], Hs[(k + kq) * LDH + 16 * (tt % FT) + l16],
                                       accW1[q]);
@@ -314,40 +333,29 @@ __global__ __launch_bounds__(NT) void head_train_kernel(HeadTrainP p) {
     }
 
     // this workgroup's partial
-    float* out = p.part + (int64_t)blockIdx.x * T::P_STRIDE;
+    float* out = p.part + (int64_t)blockIdx.x * PT::P_STRIDE;
 #pragma unroll
-    for (int q = 0; q < T::QW1; ++q) {
+    for (int q = 0; q < QW1; ++q) {
         const int tt = wave + 8 * q, ht = tt / (F / 16), ft = tt % (F / 16);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[T::P_DW1 + (16 * ht + 4 * kq + r) * F + 16 * ft + l16] = accW1[q][r];
+        for (int r = 0; r < 4; ++r) out[PT::P_DW1 + (16 * ht + 4 * kq + r) * F + 16 * ft + l16] = accW1[q][r];
     }
 #pragma unroll
-    for (int q = 0; q < T::QW2; ++q) {
+    for (int q = 0; q < QW2; ++q) {
         const int tt = wave + 8 * q, ct = tt / (H / 16), ht = tt % (H / 16);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[T::P_DW2 + (16 * ct + 4 * kq + r) * H + 16 * ht + l16] = accW2[q][r];
+        for (int r = 0; r < 4; ++r) out[PT::P_DW2 + (16 * ct + 4 * kq + r) * H + 16 * ht + l16] = accW2[q][r];
     }
-    if (tid < H) out[T::P_DB1 + tid] = dbias;
-    if (tid >= 256 && tid < 256 + TC) out[T::P_DB2 + tid - 256] = dbias;
-    // loss: lanes in order within the wave, then waves in order
-    float v = lossp;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    if (tid == 0) {
-        float s = 0.f;
-        for (int w = 0; w < NT / 64; ++w) s += red[w];
-        out[T::P_LOSS] = s * p.lw;
-    }
+    if (tid < H) out[PT::P_DB1 + tid] = dbias;
+    if (tid >= 256 && tid < 256 + TC) out[PT::P_DB2 + tid - 256] = dbias;
+    block_loss(lossp, p.lw, &out[PT::P_LOSS]);
 }
 
 // grads[i] = sum over workgroups of part[b][i], i <= P_LOSS: dW1, db1, dW2 (C rows), db2, loss. A block owns 32
 // consecutive entries; its 8 thread groups take every 8th partial and are combined in group order (deterministic).
-template <int F>
+template <class T>
 __global__ __launch_bounds__(256) void head_train_reduce_kernel(int nparts, int C, const float* part, float* grads,
                                                                 float* loss) {
-    using T = HT<F>;
     constexpr int H = T::H;
     __shared__ float acc_s[8][32];
     const int c = threadIdx.x & 31, grp = threadIdx.x >> 5;
@@ -366,23 +374,15 @@ __global__ __launch_bounds__(256) void head_train_reduce_kernel(int nparts, int 
     else loss[0] = s;
 }
 
-template <int F>
-int grid_of(int64_t M) {
-    const int64_t ntiles = (M + HT<F>::TR - 1) / HT<F>::TR;
+// one workgroup per CU, fewer when there are fewer tiles of TR rows
+int grid_of(int64_t M, int TR) {
+    const int64_t ntiles = (M + TR - 1) / TR;
     return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, 256));
 }
 
-template <int F>
-int launch(const HeadTrainP& p, int64_t C, float* grads, float* loss, hipStream_t s) {
-    const int grid = grid_of<F>(p.M);
-    hipLaunchKernelGGL(head_train_kernel<F>, dim3((unsigned)grid), dim3(NT), 0, s, p);
-    hipLaunchKernelGGL(head_train_reduce_kernel<F>, dim3((HT<F>::P_LOSS + 1 + 31) / 32), dim3(256), 0, s, grid, (int)C,
-                       (const float*)p.part, grads, loss);
-    return pg::check_launch("pg_head_train_f32");
-}
-
 // F = 256 (config 5) is not taken: its 128 KB W1 does not fit the LDS beside the tiles, and read from L2 per MFMA
-// operand the kernel measured 760 us against ~0.66 ms for the framework ops it would replace (round 5)
+// operand this kernel (32-row tiles then) measured 760 us against ~0.66 ms for the framework ops it would replace
+// (round 5)
 bool shape_ok(int64_t F, int64_t H, int64_t C) { return F == 128 && H == F / 2 && C >= 1 && C <= TC; }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -417,8 +417,7 @@ constexpr int W1B = 2 * H * RW1 * 2, HB = TR * RH * 2, AB = 2 * TR * RA * 2, LB 
 constexpr int LDS_BYTES = W1B + HB + 2 * AB + LB;
 static_assert(LDS_BYTES <= 163840, "LDS");
 static_assert(TR * F * 2 <= AB, "dh staging fits the a image");
-constexpr int P_DW1 = 0, P_DB1 = H * F, P_DW2 = P_DB1 + H, P_DB2 = P_DW2 + TC * H, P_LOSS = P_DB2 + TC;
-constexpr int P_STRIDE = (P_LOSS + 1 + 3) / 4 * 4;
+using PT = Part<F>;
 }  // namespace h5
 
 __device__ __forceinline__ void split2(float v, uint16_t& hi, uint16_t& lo) {
@@ -437,6 +436,10 @@ __device__ __forceinline__ f32x4 mfma16k(s16x4 a, s16x4 b, f32x4 c) {
 // q); lane 4q + p supplies the address of row q, columns 4p .. 4p + 3
 __device__ __forceinline__ s16x4 tr16(const void* p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+}
+__device__ __forceinline__ uint4 pack8(const uint16_t (&e)[8]) {
+    return make_uint4(e[0] | (uint32_t)e[1] << 16, e[2] | (uint32_t)e[3] << 16, e[4] | (uint32_t)e[5] << 16,
+                      e[6] | (uint32_t)e[7] << 16);
 }
 __device__ __forceinline__ uint4 cat8(s16x4 a, s16x4 b) {
     const uint2 x = __builtin_bit_cast(uint2, a), y = __builtin_bit_cast(uint2, b);
@@ -481,19 +484,15 @@ __global__ __launch_bounds__(NT) void head_train5_kernel(HeadTrainP p, const uin
             uint16_t hi[8], lo[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) split2(c < p.C ? p.W2[c * H + 32 * s + 8 * g + e] : 0.f, hi[e], lo[e]);
-            w2t[0][s] = make_uint4(hi[0] | (uint32_t)hi[1] << 16, hi[2] | (uint32_t)hi[3] << 16, hi[4] | (uint32_t)hi[5] << 16,
-                                   hi[6] | (uint32_t)hi[7] << 16);
-            w2t[1][s] = make_uint4(lo[0] | (uint32_t)lo[1] << 16, lo[2] | (uint32_t)lo[3] << 16, lo[4] | (uint32_t)lo[5] << 16,
-                                   lo[6] | (uint32_t)lo[7] << 16);
+            w2t[0][s] = pack8(hi);
+            w2t[1][s] = pack8(lo);
         }
         const int j = 16 * wave + l16;
         uint16_t hi[8], lo[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) split2(8 * g + e < p.C ? p.W2[(8 * g + e) * H + j] : 0.f, hi[e], lo[e]);
-        w2b[0] = make_uint4(hi[0] | (uint32_t)hi[1] << 16, hi[2] | (uint32_t)hi[3] << 16, hi[4] | (uint32_t)hi[5] << 16,
-                            hi[6] | (uint32_t)hi[7] << 16);
-        w2b[1] = make_uint4(lo[0] | (uint32_t)lo[1] << 16, lo[2] | (uint32_t)lo[3] << 16, lo[4] | (uint32_t)lo[5] << 16,
-                            lo[6] | (uint32_t)lo[7] << 16);
+        w2b[0] = pack8(hi);
+        w2b[1] = pack8(lo);
     }
     const float b1j = p.b1[16 * wave + l16];
     const float b2c = (wave < 2 && 16 * wave + l16 < p.C) ? p.b2[16 * wave + l16] : 0.f;
@@ -680,18 +679,17 @@ __global__ __launch_bounds__(NT) void head_train5_kernel(HeadTrainP p, const uin
 
     // this workgroup's partial: dW1 rows 16 w + 4 g + r, columns 16 ft + l16; dW2 rows 16 ct + 4 g + r, columns
     // 16 w + l16; db1 (column j = 16 w + l16: the four row groups g in order); db2 (classes: the 16 rows in order)
-    float* out = p.part + (int64_t)blockIdx.x * P_STRIDE;
+    float* out = p.part + (int64_t)blockIdx.x * PT::P_STRIDE;
 #pragma unroll
     for (int ft = 0; ft < F / 16; ++ft)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[P_DW1 + (16 * wave + 4 * g + r) * F + 16 * ft + l16] = accW1[ft][r];
+        for (int r = 0; r < 4; ++r) out[PT::P_DW1 + (16 * wave + 4 * g + r) * F + 16 * ft + l16] = accW1[ft][r];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) out[P_DW2 + (16 * ct + 4 * g + r) * H + 16 * wave + l16] = accW2[ct][r];
+        for (int r = 0; r < 4; ++r) out[PT::P_DW2 + (16 * ct + 4 * g + r) * H + 16 * wave + l16] = accW2[ct][r];
     __syncthreads();
     float* red = reinterpret_cast<float*>(LF);  // [16][32] scratch (the tile loop is done with it)
-    __shared__ float redw[NT / 64];
     if (tid < 256) red[tid] = 0.f;
     __syncthreads();
     {  // db1: g = 0..3 in order
@@ -699,52 +697,46 @@ __global__ __launch_bounds__(NT) void head_train5_kernel(HeadTrainP p, const uin
             if (g == gg) red[16 * wave + l16] += db1p;
             __syncthreads();
         }
-        if (tid < H) out[P_DB1 + tid] = red[tid];
+        if (tid < H) out[PT::P_DB1 + tid] = red[tid];
         __syncthreads();
         red[tid] = db2p;  // db2: thread (row tid >> 5, class tid & 31)
         __syncthreads();
         if (tid < TC) {
             float s_ = 0.f;
             for (int r = 0; r < TR; ++r) s_ += red[r * 32 + tid];
-            out[P_DB2 + tid] = s_;
+            out[PT::P_DB2 + tid] = s_;
         }
     }
-    float v = lossp;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) redw[wave] = v;
-    __syncthreads();
-    if (tid == 0) {
-        float s_ = 0.f;
-        for (int w = 0; w < NT / 64; ++w) s_ += redw[w];
-        out[P_LOSS] = s_ * p.lw;
-    }
+    block_loss(lossp, p.lw, &out[PT::P_LOSS]);
 }
 
-// the F = 256 partials summed as head_train_reduce_kernel does for F = 128
-__global__ __launch_bounds__(256) void head_train5_reduce_kernel(int nparts, int C, const float* part, float* grads,
-                                                                 float* loss) {
-    using namespace h5;
-    __shared__ float acc_s[8][32];
-    const int c = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + c;
-    float s = 0.f;
-    if (i <= P_LOSS)
-        for (int b = grp; b < nparts; b += 8) s += part[(int64_t)b * P_STRIDE + i];
-    acc_s[grp][c] = s;
-    __syncthreads();
-    if (grp != 0 || i > P_LOSS) return;
-    s = acc_s[0][c];
-    for (int g = 1; g < 8; ++g) s += acc_s[g][c];
-    if (i < P_DW2) grads[i] = s;
-    else if (i < P_DB2) { if ((i - P_DW2) / H < C) grads[i] = s; }
-    else if (i < P_LOSS) { if (i - P_DB2 < C) grads[P_DW2 + C * H + (i - P_DB2)] = s; }
-    else loss[0] = s;
+// What both entries do once the shape is taken: the argument checks in their order (null arguments, row lengths, the
+// entry's layout decline -- `layout`, null when it takes the layout --, drop_p, seed, workspace: `need` floats) and the
+// kernel parameters but for h and dh.
+int prepare(HeadTrainP& p, int64_t M, int64_t F, int64_t C, const void* h, int64_t ldh, const float* W1, const float* b1,
+            const float* W2, const float* b2, const int64_t* y, float loss_weight, float drop_p, const int64_t* seed,
+            const float* grad_scale, const void* dh, int64_t lddh, const float* grads, const float* loss, float* work,
+            int64_t work_floats, int64_t need, const char* layout) {
+    PG_REQUIRE(M >= 0 && h && W1 && b1 && W2 && b2 && y && dh && grads && loss && work, "null argument");
+    PG_REQUIRE(ldh >= F && lddh >= F, "h, dh: rows of F elements");
+    if (layout) return pg::set_error(PG_ERR_UNSUPPORTED, "%s", layout);  // declined before any launch, as a shape is
+    PG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "drop_p in [0, 1)");
+    PG_REQUIRE(drop_p == 0.f || seed, "dropout needs a seed");
+    PG_REQUIRE(work_floats >= need, "workspace too small");
+    const uint32_t thr = drop_p > 0.f ? (uint32_t)std::min(16777215.0, std::ceil((double)drop_p * 16777216.0)) : 0u;
+    p = HeadTrainP{M, (int)C, nullptr, ldh, W1, b1, W2, b2, y, loss_weight, thr, drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.f,
+                   seed, grad_scale, nullptr, lddh, work};
+    return PG_OK;
 }
 
-int grid5(int64_t M) {
-    const int64_t ntiles = (M + h5::TR - 1) / h5::TR;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(ntiles, 256));
+// the training kernel (`kernel(grid)` starts it) and, behind it, the reduction of its grid's partials
+template <class PT, class Kernel>
+int launch(const char* who, int grid, const float* part, int64_t C, float* grads, float* loss, hipStream_t s,
+           Kernel kernel) {
+    kernel(grid);
+    hipLaunchKernelGGL(head_train_reduce_kernel<PT>, dim3((PT::P_LOSS + 1 + 31) / 32), dim3(256), 0, s, grid, (int)C,
+                       part, grads, loss);
+    return pg::check_launch(who);
 }
 
 }  // namespace
@@ -753,7 +745,7 @@ extern "C" {
 
 int64_t pg_head_train_bf16_workspace(int64_t M, int64_t F, int64_t H, int64_t C) {
     if (M < 0 || F != h5::F || H != h5::H || C < 1 || C > TC) return -1;
-    return (int64_t)grid5(M) * h5::P_STRIDE;
+    return (int64_t)grid_of(M, h5::TR) * h5::PT::P_STRIDE;
 }
 
 int pg_head_train_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uint16_t* h, int64_t ldh, const float* W1,
@@ -762,31 +754,13 @@ int pg_head_train_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uint16_
                        float* grads, float* loss, float* work, int64_t work_floats, void* stream) {
     if (F != h5::F || H != h5::H || C < 1 || C > TC)
         return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_bf16: F = 256, H = 128, C <= 32 only");
-    PG_REQUIRE(M >= 0 && h && W1 && b1 && W2 && b2 && y && dh && grads && loss && work, "null argument");
-    PG_REQUIRE(ldh >= F && lddh >= F, "h, dh: rows of F elements");
-    // a layout the 16-B row pieces do not take is a legal argument: declined before any launch, as a shape is
-    if (ldh % 8 || lddh % 8 || !pg::aligned16(h) || !pg::aligned16(dh) || !pg::aligned16(W1))
-        return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_bf16: needs ldh, lddh multiples of 8 and 16-B aligned "
-                                                 "h, dh, W1");
-    PG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "drop_p in [0, 1)");
-    PG_REQUIRE(drop_p == 0.f || seed, "dropout needs a seed");
-    PG_REQUIRE(work_floats >= pg_head_train_bf16_workspace(M, F, H, C), "workspace too small");
-    HeadTrainP p{};
-    p.M = M;
-    p.C = (int)C;
-    p.ldh = ldh;
-    p.W1 = W1;
-    p.b1 = b1;
-    p.W2 = W2;
-    p.b2 = b2;
-    p.y = y;
-    p.lw = loss_weight;
-    p.drop_thr = drop_p > 0.f ? (uint32_t)std::min(16777215.0, std::ceil((double)drop_p * 16777216.0)) : 0u;
-    p.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.f;
-    p.seed = seed;
-    p.scale = grad_scale;
-    p.lddh = lddh;
-    p.part = work;
+    // a layout the 16-B row pieces do not take is a legal argument
+    const bool taken = !(ldh % 8 || lddh % 8 || !pg::aligned16(h) || !pg::aligned16(dh) || !pg::aligned16(W1));
+    HeadTrainP p;
+    if (int rc = prepare(p, M, F, C, h, ldh, W1, b1, W2, b2, y, loss_weight, drop_p, seed, grad_scale, dh, lddh, grads,
+                         loss, work, work_floats, pg_head_train_bf16_workspace(M, F, H, C),
+                         taken ? nullptr : "pg_head_train_bf16: needs ldh, lddh multiples of 8 and 16-B aligned h, dh, W1"))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     static bool attr_set = false;  // dynamic LDS above the 64 KiB default (set once; idempotent)
     if (!attr_set) {
@@ -795,16 +769,14 @@ int pg_head_train_bf16(int64_t M, int64_t F, int64_t H, int64_t C, const uint16_
             return pg::set_error(PG_ERR_HIP, "pg_head_train_bf16: cannot raise the LDS limit");
         attr_set = true;
     }
-    const int grid = grid5(M);
-    hipLaunchKernelGGL(head_train5_kernel, dim3((unsigned)grid), dim3(NT), h5::LDS_BYTES, s, p, h, dh);
-    hipLaunchKernelGGL(head_train5_reduce_kernel, dim3((h5::P_LOSS + 1 + 31) / 32), dim3(256), 0, s, grid, (int)C,
-                       (const float*)p.part, grads, loss);
-    return pg::check_launch("pg_head_train_bf16");
+    return launch<h5::PT>("pg_head_train_bf16", grid_of(M, h5::TR), work, C, grads, loss, s, [&](int grid) {
+        hipLaunchKernelGGL(head_train5_kernel, dim3((unsigned)grid), dim3(NT), h5::LDS_BYTES, s, p, h, dh);
+    });
 }
 
 int64_t pg_head_train_workspace(int64_t M, int64_t F, int64_t H, int64_t C) {
     if (M < 0 || !shape_ok(F, H, C)) return -1;
-    return (int64_t)grid_of<128>(M) * HT<128>::P_STRIDE;
+    return (int64_t)grid_of(M, h3::TR) * h3::PT::P_STRIDE;
 }
 
 int pg_head_train_f32(int64_t M, int64_t F, int64_t H, int64_t C, const float* h, int64_t ldh, const float* W1,
@@ -813,33 +785,18 @@ int pg_head_train_f32(int64_t M, int64_t F, int64_t H, int64_t C, const float* h
                       float* grads, float* loss, float* work, int64_t work_floats, void* stream) {
     if (!shape_ok(F, H, C))
         return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_f32: F = 128, H = 64, C <= 32 only");
-    PG_REQUIRE(M >= 0 && h && W1 && b1 && W2 && b2 && y && dh && grads && loss && work, "null argument");
-    PG_REQUIRE(ldh >= F && lddh >= F, "h, dh: rows of F floats");
-    if (ldh % 4 || !pg::aligned16(h))  // a legal layout the 16-B loads of h do not take: declined before any launch
-        return pg::set_error(PG_ERR_UNSUPPORTED, "pg_head_train_f32: needs ldh a multiple of 4 and a 16-B aligned h");
-    PG_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "drop_p in [0, 1)");
-    PG_REQUIRE(drop_p == 0.f || seed, "dropout needs a seed");
-    PG_REQUIRE(work_floats >= pg_head_train_workspace(M, F, H, C), "workspace too small");
-    HeadTrainP p{};
-    p.M = M;
-    p.C = (int)C;
+    const bool taken = !(ldh % 4 || !pg::aligned16(h));  // a legal layout the 16-B loads of h do not take
+    HeadTrainP p;
+    if (int rc = prepare(p, M, F, C, h, ldh, W1, b1, W2, b2, y, loss_weight, drop_p, seed, grad_scale, dh, lddh, grads,
+                         loss, work, work_floats, pg_head_train_workspace(M, F, H, C),
+                         taken ? nullptr : "pg_head_train_f32: needs ldh a multiple of 4 and a 16-B aligned h"))
+        return rc;
     p.h = h;
-    p.ldh = ldh;
-    p.W1 = W1;
-    p.b1 = b1;
-    p.W2 = W2;
-    p.b2 = b2;
-    p.y = y;
-    p.lw = loss_weight;
-    p.drop_thr = drop_p > 0.f ? (uint32_t)std::min(16777215.0, std::ceil((double)drop_p * 16777216.0)) : 0u;
-    p.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.f;
-    p.seed = seed;
-    p.scale = grad_scale;
     p.dh = dh;
-    p.lddh = lddh;
-    p.part = work;
     hipStream_t s = (hipStream_t)stream;
-    return launch<128>(p, C, grads, loss, s);
+    return launch<h3::PT>("pg_head_train_f32", grid_of(M, h3::TR), work, C, grads, loss, s, [&](int grid) {
+        hipLaunchKernelGGL(head_train_kernel, dim3((unsigned)grid), dim3(NT), 0, s, p);
+    });
 }
 
 }  // extern "C"

@@ -403,6 +403,27 @@ def test_head_kernel_vs_torch(pkg, cuda, F, H, C):
     assert_close(emb, emb_ref, "emb")
 
 
+@pytest.mark.parametrize("F,H,C,M", [(128, 64, 20, 33), (32, 16, 5, 32833), (256, 128, 50, 16449)])
+def test_head_second_tile_and_row_past_a_tile(pkg, cuda, F, H, C, M):
+    """ops.head against a float64 reference where test_head_kernel_vs_torch's 1000 rows do not reach: the model-shape
+    kernel ending one row past a 32-row tile (M = 33), and a persistent head_kernel block walking a second 64-row tile
+    (514 tiles on the 512 slots of the F <= 128 instantiation, 258 on the 256 of the F <= 256 one), the last tile of
+    one row."""
+    from protgram_directgcn_amd import ops
+    g = torch.Generator().manual_seed(F * 1000 + C + M)
+    h = torch.randn(M, F, generator=g)
+    W1, b1 = torch.randn(H, F, generator=g) * 0.2, torch.randn(H, generator=g) * 0.1
+    W2, b2 = torch.randn(C, H, generator=g) * 0.2, torch.randn(C, generator=g) * 0.1
+    hd = h.double()
+    z = torch.relu(hd @ W1.double().t() + b1.double())
+    lp_ref = torch.log_softmax(z @ W2.double().t() + b2.double(), dim=-1)
+    emb_ref = hd / (torch.norm(hd, p=2, dim=1, keepdim=True) + 1e-12)
+    lp, emb = ops.head(h.to(cuda), W1.to(cuda), b1.to(cuda), W2.to(cuda), b2.to(cuda), 1e-12)
+    assert lp.shape == (M, C) and emb.shape == (M, F)
+    assert_close(lp, lp_ref, "log_probs")
+    assert_close(emb, emb_ref, "emb")
+
+
 @pytest.mark.parametrize("name", ["f1_fasta2", "f3_bench", "f6_pe1"])
 def test_model_inference_path_vs_reference(pkg, cuda, name):
     """eval + no_grad: the extract_gcn_node_embeddings path (models_utils.py:265-273), fused head kernel."""

@@ -1,7 +1,7 @@
-"""Bit-identity probe of the dense backward (or, with --forward, the dense forward) between two builds of the library
-(a refactor's parent and its branch).
+"""Bit-identity probe of the dense backward (or, with --forward, the dense forward; with --head, the prediction head)
+between two builds of the library (a refactor's parent and its branch).
 
-    python tools/dense_bwd_bits.py [--forward] PARENT_LIB BRANCH_LIB [--out FILE] [--dir DIR] [--timeout SECONDS]
+    python tools/dense_bwd_bits.py [--forward | --head] PARENT_LIB BRANCH_LIB [--out FILE] [--dir DIR] [--timeout SECONDS]
 
 For each library one fresh child process (PG_DIRECTGCN_LIB set to it) runs the case list below on the seeded
 tests/test_gpu_parity._dense_case inputs, every case with dropout 0 and 0.3, and writes the bytes of every tensor
@@ -14,6 +14,10 @@ is started.
 at FWD_X3P_M rows and the 32-row one (F_in 64 with W_res) at FWD_X3_M, both gate modes, constant / identity residual /
 pre-gated operand on and off, dropout 0 and 0.3, each under FWD_FLAGS; packed and unpacked weights; the n-gram row map.
 Outputs above 64 KiB are dumped as their SHA-256 and length.
+
+--head: ops.head, ops.head_train and ops.head_train_bf16 instead (child_head below) at the shapes and row counts of
+HEAD_CASES, HEAD_TRAIN_M and HEAD_TRAIN5_M: logp and emb; loss, dh and the four decoder gradients with dropout 0 and 0.5,
+without and with a loss scale. Every kernel of the head is deterministic, so every tensor must be byte-equal.
 """
 from __future__ import annotations
 
@@ -144,6 +148,72 @@ def child_forward(outdir: str) -> int:
     return 0
 
 
+# ops.head: ((F, H, C), bf16 h?, row counts). Model shape (head_x3_kernel, 32-row tiles): a one-row tile, one row short of
+# a tile, one tile, one tile and a row; head_kernel (64-row tiles, persistent): 514 tiles on 512 slots and 258 on 256, so
+# a block walks a second tile; the last three shapes run the generic kernel
+HEAD_CASES = ([((128, 64, C), bf, (1, 31, 32, 33, 1000)) for C in (20, 32, 1) for bf in (False, True)] +
+              [((32, 16, 5), False, (1, 63, 65, 32833)), ((64, 32, 5), True, (1, 63, 65, 32833)),
+               ((256, 128, 50), False, (65, 16449))] +
+              [(shape, False, (1, 5)) for shape in ((16, 8, 400), (34, 17, 3), (12, 6, 1))])
+HEAD_TRAIN_M = (1, 63, 64, 65, 16449)   # (128, 64, C in 1, 20, 32): 258 tiles of 64 rows on 256 workgroups
+HEAD_TRAIN5_M = (1, 15, 16, 17, 4113)   # (256, 128, 20): 258 tiles of 16 rows
+HEAD_DROPS = (0.0, 0.5)
+
+
+def child_head(outdir: str) -> int:
+    import itertools
+
+    sys.path.insert(0, REPO)
+    import torch
+    from __graft_entry__ import load_package
+    load_package()
+    from protgram_directgcn_amd import ops
+
+    dev = torch.device("cuda:0")
+    os.makedirs(outdir, exist_ok=True)
+
+    def save(name, t):
+        b = t.detach().reshape(-1).contiguous().cpu().view(torch.uint8).numpy().tobytes()  # the loss is 0-d
+        if len(b) > 65536:
+            b = f"sha256 {hashlib.sha256(b).hexdigest()} of {len(b)} bytes\n".encode()
+        with open(os.path.join(outdir, name + ".bin"), "wb") as f:
+            f.write(b)
+
+    def decoder(g, F, H, C):  # as tests/test_gpu_parity.py's head tests draw it
+        return [t.to(dev) for t in (torch.randn(H, F, generator=g) * 0.2, torch.randn(H, generator=g) * 0.1,
+                                    torch.randn(C, H, generator=g) * 0.2, torch.randn(C, generator=g) * 0.1)]
+
+    for (F, H, C), bf, Ms in HEAD_CASES:
+        for M in Ms:
+            g = torch.Generator().manual_seed(F * 1000 + C + M)
+            h = torch.randn(M, F, generator=g)
+            h[M // 2] = 0.0  # zero row: emb = 0 / (0 + eps)
+            h = h.to(dev).to(torch.bfloat16) if bf else h.to(dev)
+            lp, emb = ops.head(h, *decoder(g, F, H, C), 1e-12)
+            tag = f"head_{F}x{H}x{C}_{'bf16' if bf else 'f32'}_M{M}"
+            save(tag + ".logp", lp)
+            save(tag + ".emb", emb)
+    trains = [(ops.head_train, "head_train", 128, 64, C, HEAD_TRAIN_M, torch.float32) for C in (1, 20, 32)]
+    trains.append((ops.head_train_bf16, "head_train_bf16", 256, 128, 20, HEAD_TRAIN5_M, torch.bfloat16))
+    for fn, name, F, H, C, Ms, dt in trains:
+        for M, drop, scaled in itertools.product(Ms, HEAD_DROPS, (False, True)):
+            g = torch.Generator().manual_seed(M + C)
+            h = torch.randn(M, F, generator=g).to(dt).to(dev)
+            W = decoder(g, F, H, C)
+            y = torch.randint(0, C, (M,), generator=g).to(dev)
+            seed = torch.tensor([0x1234_5678_9abc_def0 + M], dtype=torch.int64, device=dev)
+            r = fn(h, *W, y, 0.75, drop, seed if drop else None, torch.tensor(1024.0, device=dev) if scaled else None)
+            if r is None:
+                print(f"{name} C={C} M={M}: the entry point does not take this case", file=sys.stderr)
+                return 2
+            loss, dh, grads = r
+            tag = f"{name}_C{C}_M{M}.drop{drop}.scale{int(scaled)}"
+            for key, t in zip(("loss", "dh", "dW1", "db1", "dW2", "db2"), (loss, dh) + tuple(grads)):
+                save(f"{tag}.{key}", t)
+    torch.cuda.synchronize()
+    return 0
+
+
 def child(outdir: str) -> int:
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "tests"))
@@ -211,10 +281,12 @@ def main() -> int:
     ap.add_argument("--dir", default=os.path.join(tempfile.gettempdir(), "dense_bwd_bits"), help="tensor dumps")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per child")
     ap.add_argument("--forward", action="store_true", help="the dense forward instead (child_forward)")
+    ap.add_argument("--head", action="store_true", help="the prediction head instead (child_head)")
     ap.add_argument("--child", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    mode = ["--forward"] if a.forward else ["--head"] if a.head else []
     if a.child:
-        return child_forward(a.child) if a.forward else child(a.child)
+        return child_forward(a.child) if a.forward else child_head(a.child) if a.head else child(a.child)
     dirs = {}
     for tag, lib in (("parent", a.parent_lib), ("branch", a.branch_lib)):
         dirs[tag] = os.path.join(a.dir, tag)
@@ -223,7 +295,7 @@ def main() -> int:
         env.pop("PG_SPMM_FLAGS", None)
         try:
             rc = subprocess.run([sys.executable, os.path.abspath(__file__), lib, lib, "--child", dirs[tag]] +
-                                (["--forward"] if a.forward else []), env=env, timeout=a.timeout).returncode
+                                mode, env=env, timeout=a.timeout).returncode
         except subprocess.TimeoutExpired:
             rc = 124
         if rc != 0:
@@ -243,8 +315,9 @@ def main() -> int:
             verdict += f"  {len(da)} bytes"
         bad += not verdict.startswith("equal")
         lines.append(f"{n[:-4]:60s} {verdict}")
-    what = "the forward cases" if a.forward else f"{len(CASES)} cases"
-    lines.append(f"{len(names)} tensors of {what} (dropout {DROPS[0]} and {DROPS[1]}): "
+    what = "the forward cases" if a.forward else "the head cases" if a.head else f"{len(CASES)} cases"
+    drops = HEAD_DROPS if a.head else DROPS
+    lines.append(f"{len(names)} tensors of {what} (dropout {drops[0]} and {drops[1]}): "
                  f"{len(names) - bad} equal, {bad} DIFFERS")
     report = "\n".join(lines)
     print(report)
