@@ -578,6 +578,28 @@ int pg_pca_moments_f64(const float* X, int64_t ldx, int64_t P, int64_t F, const 
 int pg_pca_project(const float* X, int64_t ldx, int64_t P, int64_t F, const int32_t* counts, const float* center,
                    const float* W, int64_t k, void* out, int64_t ldo, int out_dtype, void* stream);
 
+/* ---- Louvain local moving (the trainer's community task labels, protgram_directgcn_trainer.py:200-220, and its
+ * fallback partitioner, :159-170) ----------------------------------------------------------------------------------
+ * One synchronous sweep over a symmetric CSR with positive int64 weights (rowptr [n_rows + 1], col and w [nnz]; both
+ * directions of an edge present, col in [0, n_rows)). k [n_rows]: node strengths; comm_in [n_rows]: the community of
+ * every node, ids in [0, n_rows); tot / size [n_rows]: per community the sum of its members' strengths and their
+ * number; two_m: the sum of all strengths, below 2^62. Every decision is taken from these inputs, none from
+ * comm_out, so the result does not depend on scheduling. Row i is active when
+ *   ((uint64_t)i * 0x9E3779B97F4A7C15 mod 2^64) >> 32, reduced mod `classes`, equals `cls`;
+ * inactive rows copy comm_in. For an active row and every community c among its neighbours j != i (a diagonal
+ * entry is skipped), with w_ic the sum of W_ij over the neighbours in c:
+ *   gain(c) = two_m * w_ic - (tot[c] - [c == comm_in[i]] * k[i]) * k[i]        (128-bit integer arithmetic)
+ * The row moves to the candidate c != comm_in[i] of largest gain, the smallest id among equal gains, when that gain
+ * is strictly larger than gain(comm_in[i]) (w = 0 there when no neighbour shares the row's community). A row whose
+ * community has size 1 takes no community of size 1 and larger id as a candidate. *moved (device int64, not cleared
+ * here) grows by the number of rows that moved. comm_out must not overlap comm_in. Rows of up to 64 entries take a
+ * wave each, rows of up to pg_louvain_row_capacity() entries a workgroup with a hash table in LDS, longer rows a
+ * workgroup with passes over ranges of community ids: exact for every row. */
+int64_t pg_louvain_row_capacity(void);
+int pg_louvain_move_i64(int64_t n_rows, const int64_t* rowptr, const int64_t* col, const int64_t* w, const int64_t* k,
+                        const int64_t* comm_in, const int64_t* tot, const int64_t* size, int64_t two_m, int classes,
+                        int cls, int64_t* comm_out, int64_t* moved, void* stream);
+
 /* ---- training-step helpers (the trainer's L2 term over all parameters, trainer :96 / :136) ---------
  * A tensor list is a device array of descriptors; tensor t is split into pg_multi_chunks(numel_t) chunks of
  * 16K elements and chunk_ptr[t] = the first chunk of tensor t (exclusive prefix sum, chunk_ptr[ntens] =

@@ -146,6 +146,9 @@ SIGNATURES = {
     "pg_ngram_letter_masks": (ctypes.c_int, [c_i64, c_vp, ctypes.c_int, c_i64, c_vp, c_vp, c_vp]),
     "pg_reach_hop_u32": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_i64, c_vp,
                                         c_vp, c_vp]),
+    "pg_louvain_row_capacity": (c_i64, []),
+    "pg_louvain_move_i64": (ctypes.c_int, [c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int,
+                                           ctypes.c_int, c_vp, c_vp, c_vp]),
     "pg_pool_distinct_max_nodes": (c_i64, []),
     "pg_pool_rows_f32": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_i64,
                                         c_vp, c_u32, c_vp]),

@@ -7,8 +7,9 @@ The reference partitions the graph with METIS (or Louvain), then for every clust
 (:178-197) -- a scan of all E entries per cluster. Here:
 
 * ``cluster_count`` is the reference's cluster-count rule (:154-156);
-* ``range_clusters`` replaces METIS/Louvain (neither is installed) with contiguous ranges of a
-  node order. With a graph's locality schedule as the order (``CSRGraph.row_order``: rows sorted by
+* ``louvain_clusters`` is the reference's fallback partitioner (:159-175, Louvain when METIS is absent) on the
+  GPU (community.py, DESIGN §11);
+* ``range_clusters`` stands in for METIS (not installed) with contiguous ranges of a node order. With a graph's locality schedule as the order (``CSRGraph.row_order``: rows sorted by
   (min out-neighbour, min in-neighbour)), consecutive nodes share their neighbour sets, so the ranges keep
   many edges inside their clusters;
 * ``build_subgraphs`` extracts every cluster's three relabelled COO adjacencies in ONE pass over the edges
@@ -50,6 +51,39 @@ def range_clusters(num_nodes: int, num_clusters: int, order: Optional[torch.Tens
     parts = torch.empty(n, dtype=torch.int64, device=order.device)
     parts[order] = (torch.arange(n, device=order.device) * k) // max(n, 1)
     return parts
+
+
+def louvain_graph(num_nodes: int, ei_in, ew_in, ei_out, ew_out, frac_bits: int = 20):
+    """The graph the reference partitions (trainer :159-160) as a community.CommunityGraph: mathcal_A_out + mathcal_A_in
+    (coalesced, the float weights added in float64), of which to_networkx(to_undirected=True) keeps the entries with
+    row <= column; every weight rounded once, to nearest, to fixed point with `frac_bits` fractional bits, so that the
+    partition is exact integer work and the same on every run. An entry that rounds to 0 is no edge."""
+    from . import community
+    if not 0 <= int(frac_bits) <= 40:
+        raise ValueError("frac_bits must lie in [0, 40]")
+    n = int(num_nodes)
+    r = torch.cat([ei_out[0], ei_in[0]]).to(torch.int64)
+    c = torch.cat([ei_out[1], ei_in[1]]).to(torch.int64)
+    w = torch.cat([ew_out.reshape(-1), ew_in.reshape(-1)]).to(torch.float64)
+    if r.numel() != w.numel():
+        raise ValueError("edge weights do not match the edge indices")
+    if r.numel() and (min(int(r.min()), int(c.min())) < 0 or max(int(r.max()), int(c.max())) >= n):
+        raise IndexError(f"edge endpoints outside [0, {n})")
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("edge weights must be finite and non-negative")
+    up = r <= c
+    key, inv = torch.unique(r[up] * max(n, 1) + c[up], return_inverse=True)
+    ws = torch.zeros(key.numel(), dtype=torch.float64, device=w.device).index_add_(0, inv, w[up])
+    fixed = torch.round(ws * float(1 << int(frac_bits)))
+    return community.from_undirected(n, key // max(n, 1), key % max(n, 1), fixed)
+
+
+def louvain_clusters(num_nodes: int, ei_in, ew_in, ei_out, ew_out, frac_bits: int = 20, **kw) -> torch.Tensor:
+    """Cluster id per node from Louvain communities of louvain_graph (the reference's partitioner when METIS is
+    absent, trainer :168-175; `kw`: community.louvain's). Ids 0..C-1 in ascending order of the smallest member, which
+    is also the order in which the reference collects its clusters; feeds build_subgraphs unchanged."""
+    from . import community
+    return community.louvain(louvain_graph(num_nodes, ei_in, ew_in, ei_out, ew_out, frac_bits), **kw)
 
 
 @dataclass

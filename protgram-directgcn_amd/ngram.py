@@ -503,14 +503,37 @@ def closest_aa_labels(t: NgramTransitions, k_hops: int = 3, targets=None, rng=No
     return labels, k + 1
 
 
-def task_labels(t: NgramTransitions, task: str, **kw) -> Tuple[torch.Tensor, int]:
+def community_labels(t: NgramTransitions, **kw) -> Tuple[torch.Tensor, int]:
+    """The trainer's community task labels (protgram_directgcn_trainer.py:200-220) for all nodes at once: Louvain
+    communities of the level's undirected graph (community.combined_graph), found on the GPU by community.louvain
+    (`kw`: its classes, max_sweeps, max_levels, min_gain). No nodes: (empty, 1); no entries: (zeros, 1), as the
+    reference returns; otherwise communities 0..C-1 in ascending order of their smallest member (the reference's
+    numbers come from python-louvain's RNG), an isolated node a community of its own, num_classes = C."""
+    from . import community
+    g = community.combined_graph(t)
+    dev = g.k.device
+    if g.n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), 1
+    if g.two_m == 0:
+        return torch.zeros(g.n, dtype=torch.int64, device=dev), 1
+    labels = community.louvain(g, **kw)
+    return labels, int(labels.max()) + 1
+
+
+def task_labels(t: NgramTransitions, task: str, method: Optional[str] = None, **kw) -> Tuple[torch.Tensor, int]:
     """(labels, num_classes) of one of the trainer's self-supervised tasks (GCN_TASK_TYPES_PER_LEVEL,
-    protgram_directgcn_trainer.py:333-341)."""
+    protgram_directgcn_trainer.py:333-341). 'community' needs method='louvain': its labels are this package's
+    deterministic Louvain partition, not python-louvain's seeded one."""
+    if task != "community" and method is not None:
+        raise ValueError(f"method applies to task 'community' only, not to '{task}'")
     if task == "next_node":
         return next_node_labels(t, **kw)
     if task == "closest_aa":
         return closest_aa_labels(t, **kw)
     if task == "community":
-        raise ValueError("task 'community' needs a Louvain partition, which is out of scope here (DESIGN §7): the "
-                         "caller supplies those labels")
+        if method == "louvain":
+            return community_labels(t, **kw)
+        raise ValueError("task 'community' takes its labels from a Louvain partition, which differs from "
+                         "python-louvain's seeded one: pass method='louvain' for community_labels (DESIGN §11) or "
+                         "supply the labels")
     raise ValueError(f"Unsupported GCN_TASK_TYPE '{task}' for n={t.n}.")
