@@ -1026,22 +1026,25 @@ def head(h: torch.Tensor, W1, b1, W2, b2, eps: float):
     return logp, emb
 
 
-_LABELS_OK: dict = {}  # (data_ptr, numel, _version, C) of label tensors already checked
+_LABELS_OK: dict = {}  # (data_ptr, numel, _version, C) -> weak reference to the label tensor already checked
 
 
 def _check_labels(y: torch.Tensor, C: int):
     """Raise like F.nll_loss on a label outside [0, C) (protgram_directgcn_trainer.py:95). One host sync per label
     tensor (cached by address, size and version; the trainer's labels are fixed), none inside a HIP-graph capture,
-    where the kernel's NaN loss is the signal."""
+    where the kernel's NaN loss is the signal. The entry holds a weak reference to the tensor it checked: the
+    allocator hands a freed label tensor's address to the next one of its size (the clustered trainer's y[idx] per
+    cluster), which is another tensor and is checked itself; nothing is kept alive."""
     key = (y.data_ptr(), y.numel(), y._version, C)
-    if key in _LABELS_OK or y.numel() == 0 or torch.cuda.is_current_stream_capturing():
+    seen = _LABELS_OK.get(key)
+    if (seen is not None and seen() is y) or y.numel() == 0 or torch.cuda.is_current_stream_capturing():
         return
     lo, hi = torch.aminmax(y)
     if int(lo) < 0 or int(hi) >= C:
         raise IndexError(f"head_train: label out of range [0, {C}): min {int(lo)}, max {int(hi)}")
     if len(_LABELS_OK) > 64:
         _LABELS_OK.clear()
-    _LABELS_OK[key] = True
+    _LABELS_OK[key] = weakref.ref(y)
 
 
 def _head_train(entry: str, workspace_entry: str, h, dh_dtype, W1, b1, W2, b2, y, weight, drop_p, seed, scale):

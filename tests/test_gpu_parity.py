@@ -424,6 +424,29 @@ def test_head_second_tile_and_row_past_a_tile(pkg, cuda, F, H, C, M):
     assert_close(emb, emb_ref, "emb")
 
 
+@pytest.mark.parametrize("F,H,C", [(128, 64, 25), (32, 16, 5)])
+def test_head_hard_logits(pkg, cuda, F, H, C):
+    """ops.head where a plain exp overflows fp32: b2 carries +120 for one class and -120 for another, so the logits
+    span 240 and log(sum(exp(x))) without the row maximum is inf. head_x3_kernel (128, 64, 25) and head_kernel
+    (32, 16, 5) share row_log_softmax; against float64, whose log-probs stay finite (down to about -245)."""
+    from protgram_directgcn_amd import ops
+    g = torch.Generator().manual_seed(F * 1000 + C + 7)
+    M = 100
+    h = torch.randn(M, F, generator=g)
+    W1, b1 = torch.randn(H, F, generator=g) * 0.2, torch.randn(H, generator=g) * 0.1
+    W2, b2 = torch.randn(C, H, generator=g) * 0.2, torch.randn(C, generator=g) * 0.1
+    b2[C - 1] += 120.0
+    b2[3] -= 120.0
+    z = torch.relu(h.double() @ W1.double().t() + b1.double())
+    x = z @ W2.double().t() + b2.double()
+    lp_ref = torch.log_softmax(x, dim=-1)
+    assert bool(torch.isfinite(lp_ref).all()) and float(lp_ref.min()) < -200
+    assert not bool(torch.isfinite(x.float() - x.float().exp().sum(1, keepdim=True).log()).any())  # the naive form
+    lp, _ = ops.head(h.to(cuda), W1.to(cuda), b1.to(cuda), W2.to(cuda), b2.to(cuda), 1e-12)
+    assert lp.shape == (M, C) and bool(torch.isfinite(lp).all())
+    assert_close(lp, lp_ref, "log_probs")
+
+
 @pytest.mark.parametrize("name", ["f1_fasta2", "f3_bench", "f6_pe1"])
 def test_model_inference_path_vs_reference(pkg, cuda, name):
     """eval + no_grad: the extract_gcn_node_embeddings path (models_utils.py:265-273), fused head kernel."""
@@ -1722,21 +1745,7 @@ def test_propagate_dense_bf16_backward(pkg, cuda, n, F, res):
 
 # ---------------------------------------------------------------------------------------------------------------
 # ops.head_train (round 5): the prediction head's training step in one kernel
-def _drop_keep(seed: int, M: int, H: int, p: float):
-    """The kernel's dropout draw restated on the host (pg_head_train.hip, drop_hash): keep (m, j) when the mixed
-    index's top 24 of 32 bits are >= ceil(p 2^24)."""
-    m = np.arange(M, dtype=np.uint64)[:, None]
-    j = np.arange(H, dtype=np.uint64)[None, :]
-    with np.errstate(over="ignore"):
-        x = np.uint64(seed) ^ (np.uint64(0x9E3779B97F4A7C15) * (m * np.uint64(H) + j + np.uint64(1)))
-        x ^= x >> np.uint64(33)
-        x *= np.uint64(0xff51afd7ed558ccd)
-        x ^= x >> np.uint64(33)
-        x *= np.uint64(0xc4ceb9fe1a85ec53)
-        x ^= x >> np.uint64(33)
-    u = (x & np.uint64(0xffffffff)) >> np.uint64(8)
-    thr = min(16777215, int(np.ceil(p * 16777216.0)))
-    return torch.from_numpy(u >= np.uint64(thr))
+from head_ref import _drop_keep  # noqa: E402  the kernels' dropout draw restated on the host
 
 
 @pytest.mark.parametrize("M,drop,scaled,F", [(3001, 0.0, False, 128), (64, 0.0, False, 128), (1000, 0.5, False, 128),
